@@ -7,7 +7,19 @@ the frame's 32×32 tiles are dealt round-robin over ranks and rank 0 gathers the
 FrameBuffer spans over RCCL — total work is fixed, so scaling is strong.  The gather of frame k
 runs on a communication stream while frame k+1 renders into the other of two output buffers.
 
-Measurement windows (all after the warm-up frames):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure needs: it
+uploads the scene, renders the warm-up frames, times window 1 below, writes the last timed frame
+if `--dump-outputs DIR` is given and prints the result line.  `--full` adds the CPU baseline,
+windows 2-4, the SURVEY-model counting pass and the `roofline` / `cpu_baseline` fields of the line.
+
+`--dump-outputs DIR` writes what the last timed frame's caller receives, as float32 `.npy`:
+`rgb.npy` [n, 3] (linear colObj / spp) and `rgba8.npy` [n, 4] (the FrameBuffer bytes, 0-255), in
+packed pixel order (N > 1: only `rgba8.npy`, the frame rank 0 gathered).  A frame over the 64 MB
+budget is cut to a fixed, seeded sample of its pixels, whose packed indices go to `pixel_index.npy`
+(float64).  The scene, camera and sample sequences are fixed by the config, so two runs with the
+same arguments render the same inputs.
+
+Measurement windows (all after the warm-up frames; 2-4 only with --full):
   1. the timed region: K frames back to back, barrier + synchronize on both sides → `value`;
   2. K more frames with a HIP event pair around every kernel launch, on the stream it runs on
      (pbr_hip_set_profiling(1)) → per-kernel-family launch durations under the default schedule,
@@ -24,8 +36,8 @@ duration (window 4); traffic = rocprofv3 PMC bytes per launch of the same family
 `--serial` runs every window on the serial schedule (the command whose rocprofv3 kernel stats back
 the standalone durations, profiles/r4_*_kernel_stats.csv).
 
-The CPU baseline (rank 0, N=1) runs FIRST, in a child process started before this process touches
-the GPU: the reference itself (oracle/_ref/libpbr_ref.so, its unmodified sources built by
+The CPU baseline (--full, rank 0, N=1) runs FIRST, in a child process started before this process
+touches the GPU: the reference itself (oracle/_ref/libpbr_ref.so, its unmodified sources built by
 oracle/ref/Makefile) when that library is present — else the oracle/ restatement — on the physical
 cores of socket 0 (lscpu), pinned one thread per core, OMP_PLACES=cores OMP_PROC_BIND=close, over
 an evenly spread sample of the frame's rows; plus the reference's as-shipped 4 threads
@@ -51,6 +63,38 @@ VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2
 # shading event): reported for reference only — it counts cache-served BVH/mesh fetches as HBM
 # bytes, so it is not a bound
 B_NODE, B_PRIM, B_RAY, B_SHADE = 32, 48, 96, 64
+# --dump-outputs: at most this many bytes of .npy payload, and the seed of the pixel sample taken
+# from a frame that would exceed it
+DUMP_BUDGET_BYTES = 60_000_000
+DUMP_SEED = 20240607
+
+
+# ------------------------------------------------------------------------------- output dump
+def dump_pixel_sample(npx, budget=DUMP_BUDGET_BYTES):
+    """The packed pixel indices --dump-outputs writes: None (every pixel) when rgb + rgba8 as float32
+    (28 bytes a pixel) fit the budget, else a fixed seeded sample, sorted, that fits it together with
+    its float64 index (36 bytes a pixel)."""
+    import numpy as np
+    if npx * 28 <= budget:
+        return None
+    n = budget // 36
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(npx, n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, rgb, rgba):
+    """Write the last timed frame (device tensors rgba [n, 4] uint8 and, unless None, rgb [n, 3]
+    float32) under path."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    picks = dump_pixel_sample(rgba.shape[0])
+    if picks is not None:
+        idx = torch.from_numpy(picks).to(rgba.device)
+        rgb, rgba = (None if rgb is None else rgb.index_select(0, idx)), rgba.index_select(0, idx)
+        np.save(os.path.join(path, "pixel_index.npy"), picks.astype(np.float64))
+    if rgb is not None:
+        np.save(os.path.join(path, "rgb.npy"), rgb.cpu().numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(path, "rgba8.npy"), rgba.cpu().numpy().astype(np.float32))
 
 
 # ------------------------------------------------------------------------------- CPU baseline
@@ -241,6 +285,10 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C2")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the per-kernel / roofline windows and the SURVEY-model pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame's outputs as DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU render for the baseline")
     ap.add_argument("--no-model", action="store_true", help="skip the SURVEY-model counting pass")
@@ -260,7 +308,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # the CPU baseline runs before this process initialises the GPU
-    cpu = cpu_baseline(args.config, args.cpu_budget) if (world == 1 and not args.no_cpu_baseline) else None
+    cpu = cpu_baseline(args.config, args.cpu_budget) if (args.full and world == 1 and not args.no_cpu_baseline) else None
 
     import numpy as np
     import torch
@@ -361,19 +409,28 @@ def main():
     torch.cuda.synchronize(dev)
     # 1. the timed region
     elapsed = window(args.steps)
-    # 2. per-kernel launch durations (HIP events on each launch's stream), same K frames
-    r.set_profiling(1)
-    elapsed_ev = window(args.steps)
-    timing = r.get_profile()
-    # 3. work counters of one frame (units, algorithmic bytes)
-    r.set_profiling(2)
-    window(1)
-    counts = r.get_profile()
-    r.set_profiling(0)
+    if args.dump_outputs and rank == 0:
+        # the last timed frame: a batch's frame f lands in buffer f, a per-frame window cycles them;
+        # N > 1: the RGBA8 frame rank 0 gathered (the float spans stay on their ranks)
+        last = (frame_no[0] - 1) % nbuf if args.per_frame else args.steps - 1
+        if exchange is not None:
+            dump_outputs(args.dump_outputs, None, exchange.frame)
+        else:
+            dump_outputs(args.dump_outputs, rgbs[last], rgbas[last])
+    if args.full:
+        # 2. per-kernel launch durations (HIP events on each launch's stream), same K frames
+        r.set_profiling(1)
+        elapsed_ev = window(args.steps)
+        timing = r.get_profile()
+        # 3. work counters of one frame (units, algorithmic bytes)
+        r.set_profiling(2)
+        window(1)
+        counts = r.get_profile()
+        r.set_profiling(0)
     # 4. the same on the serial schedule: each kernel family's own launch durations
-    if args.serial:
+    if args.full and args.serial:
         timing_s, counts_s, elapsed_s = timing, counts, elapsed_ev
-    else:
+    elif args.full:
         r.set_schedule(serial=True)
         render()
         r.sync()
@@ -387,7 +444,7 @@ def main():
         r.set_schedule()
     # SURVEY §8(d) model counts: the instrumented megakernel pass (binary traversal; same tests)
     model = None
-    if not args.no_model:
+    if args.full and not args.no_model:
         st = r.render_device(rdr, rgbs[0].data_ptr(), rgbas[0].data_ptr(), stream=stream.cuda_stream, stats=True)
         torch.cuda.synchronize(dev)
         samples_rank = npx * spp
@@ -405,7 +462,7 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     value = W * H * spp / (elapsed / args.steps) / 1e6
 
-    if rank == 0:
+    if rank == 0 and args.full:
         pmc, pmc_src = pmc_traffic(args.config, build_info) if world == 1 else (None, "1 GPU only")
 
         def families(timing, counts):
@@ -493,6 +550,7 @@ def main():
                                                                 (elapsed_ev / args.steps * 1e3), 2),
                                            "families": overlapped},
                     "survey_model": model, "build": build_info}
+    if rank == 0:
         out = {
             "metric": "Msamples/sec (whole node) + wall-clock to 1080p/64spp frame; %HBM roofline",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
@@ -506,8 +564,9 @@ def main():
                                        if world > 1 else "1 GPU, whole frame (no exchange)"),
                        "schedule": "serial (one stream)" if args.serial else "default (3 chunk lanes)",
                        "frame_ms": round(ms_per_step, 3), "scene_upload_s": round(upload_s, 3)},
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = roofline
         if cpu is not None:
             out["cpu_baseline"] = cpu
             if cpu.get("value"):

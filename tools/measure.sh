@@ -17,10 +17,10 @@ for cfg in ${CONFIGS:-C2}; do
   fi
   if [ -z "${NOPROF:-}" ]; then
     (cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/prof_$lc" -o run -- python3 "$ROOT/bench.py" --config "$cfg" --steps 3 --warmup 1 --no-cpu-baseline --no-model) \
+        -d "$OUT/prof_$lc" -o run -- python3 "$ROOT/bench.py" --full --config "$cfg" --steps 3 --warmup 1 --no-cpu-baseline --no-model) \
         > "$OUT/prof_$lc.log" 2>&1 || { echo "rocprof $cfg failed"; exit 4; }
   fi
-  timeout -k 10 900 python3 bench.py --config "$cfg" ${NOCPU:+--no-cpu-baseline} ${BENCH_ARGS:-} > "$OUT/bench_$lc.log" 2>&1 \
+  timeout -k 10 900 python3 bench.py --full --config "$cfg" ${NOCPU:+--no-cpu-baseline} ${BENCH_ARGS:-} > "$OUT/bench_$lc.log" 2>&1 \
       || { echo "bench $cfg failed"; tail -5 "$OUT/bench_$lc.log"; exit 5; }
   tail -1 "$OUT/bench_$lc.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('BENCH', d['config']['workload'], d['ms_per_step'], 'ms', d['value'], 'Msamples/s; dominant', r['kernel'], 'frac', r['frac'], 'traffic_frac', r['traffic_frac'], 'cpu', (d.get('cpu_baseline') or {}).get('value'))"
 done

@@ -26,12 +26,12 @@ for cfg in ${CONFIGS:-C2}; do
   fi
   if [ -z "${NOPROF:-}" ]; then
     (cd /tmp && export TMPDIR=/tmp && timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/prof_serial_$lc" -o run -- python3 "$ROOT/bench.py" --config "$cfg" --serial --steps $S --warmup 1 \
+        -d "$OUT/prof_serial_$lc" -o run -- python3 "$ROOT/bench.py" --full --config "$cfg" --serial --steps $S --warmup 1 \
         --no-cpu-baseline --no-model) > "$OUT/prof_serial_$lc.log" 2>&1 || { echo "rocprof $cfg failed"; exit 4; }
     echo "rocprof serial $cfg ok"
     rm -f "$OUT/prof_serial_$lc/run_kernel_trace.csv"
   fi
-  timeout -k 10 1100 python3 bench.py --config "$cfg" --steps $S ${NOCPU:+--no-cpu-baseline} ${BENCH_ARGS:-} > "$OUT/bench_$lc.log" 2>&1 \
+  timeout -k 10 1100 python3 bench.py --full --config "$cfg" --steps $S ${NOCPU:+--no-cpu-baseline} ${BENCH_ARGS:-} > "$OUT/bench_$lc.log" 2>&1 \
       || { echo "bench $cfg failed"; tail -5 "$OUT/bench_$lc.log"; exit 5; }
   tail -1 "$OUT/bench_$lc.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('BENCH', d['config']['workload'], d['ms_per_step'], 'ms', d['value'], 'Msamples/s; dominant', r['kernel'], 'frac', r['frac'], r['ms_per_frame'], 'ms/frame; frame frac', r['frame']['frac'], r['frame'].get('traffic_frac'), 'cpu', (d.get('cpu_baseline') or {}).get('value'))"
 done
