@@ -745,6 +745,15 @@ class SamplerIntegrator : public Integrator {
     // Scene), renders every pixel × sample, fills m_FrameBuffer's 8-bit buffer exactly as the
     // reference (XYZ round trip, gamma, vertical flip) and its float buffer.
     void Render(const Scene& scene, double& timeConsume) override;
+    // Progressive rendering (no reference counterpart; pbr_hip_render_passes): samples
+    // [firstSample, firstSample + nSamples) of every pixel, added in sample order onto sums the
+    // integrator keeps on its device, and the image of all samples so far written to m_FrameBuffer as
+    // Render writes it.  The sampler's samplesPerPixel stays the whole budget; firstSample == 0 starts a
+    // new image, any other value must continue where the last call ended.  RenderSamples(0, k) then
+    // RenderSamples(k, spp - k) leaves Render's FrameBuffer.  Single device; integrators built on a
+    // custom (table) sampler throw.
+    void RenderSamples(const Scene& scene, int firstSample, int nSamples);
+    int SamplesDone() const { return samplesDone; }
     // Uploads the scene to the integrator's device (BVHAccel build, lights, media); Render and Li
     // do it on first use.  The reference's SamplerIntegrator::Preprocess is a no-op hook.
     virtual void Preprocess(const Scene& scene, Sampler& sampler);
@@ -789,6 +798,9 @@ class SamplerIntegrator : public Integrator {
     struct MultiGPU;
     std::shared_ptr<MultiGPU> multi;
     void RenderMulti(const Scene& scene, double& timeConsume);
+    struct Progressive;                  // RenderSamples: the carried sums and the pass's images, on the device
+    std::shared_ptr<Progressive> prog;
+    int samplesDone = 0;
 };
 class WhittedIntegrator : public SamplerIntegrator {   // Integrator/WhittedIntegrator.h
   public:

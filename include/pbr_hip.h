@@ -17,6 +17,8 @@
  *                           + HaltonSampler ctor (Sampler/Halton.cpp:30-58)
  *   pbr_hip_render        — SamplerIntegrator::Render (Integrator/Integrator.cpp:280-356), which
  *                           drives {Whitted,Path,VolPath}Integrator::Li per sample
+ *   pbr_hip_render_passes — (none; the reference renders whole frames): that Render's sample loop in
+ *                           resumable passes over a carried per-pixel sum (progressive rendering)
  *   pbr_hip_destroy       — scene/integrator destructors
  *   pbr_hip_last_error    — (none; the reference fails silently)
  *   pbr_hip_sync          — (none; the reference's Render returns when the frame is done): waits
@@ -322,6 +324,26 @@ int pbr_hip_render_frames(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int n, 
 /* Makes `stream` (hipStream_t; NULL = the context stream) wait until frame f of the last
  * pbr_hip_render_frames call is complete (e.g. before gathering it to another GPU). */
 int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f);
+/* Progressive rendering: a frame's samples in resumable passes over a carried accumulator — what
+ * SamplerIntegrator::Render's sample loop (Integrator.cpp:300-312: colObj += Li) holds after some of
+ * its iterations.  n_passes passes of samples_per_pass samples per pixel, the first pass starting at
+ * sample number first_sample; accum = 6 floats per pixel in the descriptor's packed tile order:
+ * Σ Li.rgb and Σ (Li.rgb)² over samples [0, first_sample) on entry (not read when first_sample == 0),
+ * over [0, first_sample + n_passes·samples_per_pass) on return.  desc->spp stays the sampler's
+ * samplesPerPixel — the whole budget (Sobol: rounded up to a power of two) — and the passes must end
+ * at or below it.  The carried sums continue a whole frame's in-order float additions (acc = acc + L,
+ * acc2 = acc2 + L·L), so after pass p, with k = first_sample + (p+1)·samples_per_pass samples done,
+ * rgb_outs[p] = Σ Li / k is the frame pbr_hip_render gives for a sampler whose samples 0..k-1 are these
+ * (Halton: spp = k; Sobol: power-of-two k), and with k = the budget it is pbr_hip_render's bits.
+ * rgba_outs[p] is its film transform.  Either array, or any entry, may be NULL to skip that image.
+ * The squares serve a per-pixel variance estimate: (Σ L² − (Σ L)²/k) / (k − 1).
+ * Conditions as pbr_hip_render_frames: outputs_on_device = 1, collect_stats = 0, accum a device
+ * pointer; a sample table returns PBR_E_UNSUPPORTED.  Asynchronous in the same way: passes of one
+ * call continue one rotation over the chunk lanes, a pass's write of a pixel's sums ordered after the
+ * previous pass's by events; calls on one stream follow each other, and pbr_hip_wait_frame(ctx, stream,
+ * p) orders another stream after pass p of the last call. */
+int pbr_hip_render_passes(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int first_sample, int samples_per_pass,
+                          int n_passes, float* accum, float* const* rgb_outs, uint8_t* const* rgba_outs);
 
 /* ---- schedule (no reference counterpart) ----
  * How a frame is cut into launches on the device.  Every setting renders the same bits (the GPU

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi, scenes  # noqa: F401
 
-__all__ = ["HipRenderer", "capi", "scenes", "tile_grid", "tiles_for_rank"]
+__all__ = ["HipRenderer", "ProgressiveRender", "capi", "scenes", "tile_grid", "tiles_for_rank"]
 
 
 class PbrError(RuntimeError):
@@ -107,8 +107,57 @@ class HipRenderer:
         d.collect_stats = 0
         self._check(self.lib.pbr_hip_render_frames(self.ctx, C.byref(d), n, rgb, rgba), "render_frames")
 
+    @staticmethod
+    def sample_budget(rdesc) -> int:
+        """The sampler's samplesPerPixel for rdesc.spp: Sobol rounds it up to a power of two."""
+        spp = int(rdesc.spp)
+        if rdesc.sampler == capi.SAMPLER_SOBOL and spp > 0:
+            spp = 1 << (spp - 1).bit_length()
+        return spp
+
+    def render_passes(self, rdesc, first_sample, samples_per_pass, accum_ptr, rgb_ptrs=None, rgba_ptrs=None,
+                      n_passes=None, stream: int | None = None):
+        """Sample passes over a carried accumulator (pbr_hip_render_passes): n_passes passes of
+        samples_per_pass samples per pixel from sample number first_sample, added in sample order onto
+        accum (device, 6 float32 per pixel: Σ Li.rgb, Σ Li.rgb²).  Pass p's image — the sum over all
+        samples so far divided by their count — goes to rgb_ptrs[p] / rgba_ptrs[p] (device pointers;
+        a list, or an entry, may be None).  rdesc.spp stays the whole budget.  n_passes defaults to the
+        length of the output lists.  Asynchronous, as render_frames; wait_frame(stream, p) orders
+        another stream after pass p."""
+        rgb_ptrs, rgba_ptrs = list(rgb_ptrs or []), list(rgba_ptrs or [])
+        if rgb_ptrs and rgba_ptrs and len(rgb_ptrs) != len(rgba_ptrs):
+            raise ValueError(f"render_passes: {len(rgb_ptrs)} float outputs but {len(rgba_ptrs)} RGBA8 outputs")
+        n = max(len(rgb_ptrs), len(rgba_ptrs)) if n_passes is None else int(n_passes)
+        if n < 1:
+            raise ValueError("render_passes: no passes (give n_passes or output buffers)")
+        for name, ptrs in (("rgb_ptrs", rgb_ptrs), ("rgba_ptrs", rgba_ptrs)):
+            if ptrs and len(ptrs) != n:
+                raise ValueError(f"render_passes: {len(ptrs)} {name} for {n} passes")
+        first_sample, samples_per_pass = int(first_sample), int(samples_per_pass)
+        if samples_per_pass < 1:
+            raise ValueError("render_passes: samples_per_pass must be >= 1")
+        if first_sample < 0:
+            raise ValueError("render_passes: first_sample must be >= 0")
+        if not accum_ptr:
+            raise ValueError("render_passes: accum is required (a device buffer of 6 float32 per pixel)")
+        if rdesc.sampler == capi.SAMPLER_TABLE:
+            raise ValueError("render_passes: no passes over a sample table")
+        budget = self.sample_budget(rdesc)
+        if first_sample + n * samples_per_pass > budget:
+            raise ValueError(f"render_passes: samples [{first_sample}, {first_sample + n * samples_per_pass}) run past "
+                             f"the budget of {budget} samples per pixel")
+        rgb = (C.c_void_p * n)(*[p or None for p in rgb_ptrs]) if rgb_ptrs else None
+        rgba = (C.c_void_p * n)(*[p or None for p in rgba_ptrs]) if rgba_ptrs else None
+        d = type(rdesc).from_buffer_copy(rdesc)   # (the caller's descriptor is left as it was: render_frames)
+        d.outputs_on_device = 1
+        d.stream = stream
+        d.collect_stats = 0
+        self._check(self.lib.pbr_hip_render_passes(self.ctx, C.byref(d), first_sample, samples_per_pass, n, accum_ptr,
+                                                   rgb, rgba), "render_passes")
+
     def wait_frame(self, stream: int | None, f: int):
-        """Make `stream` wait for frame f of the last render_frames call (pbr_hip_wait_frame)."""
+        """Make `stream` wait for frame f of the last render_frames call, or pass f of the last
+        render_passes call (pbr_hip_wait_frame)."""
         self._check(self.lib.pbr_hip_wait_frame(self.ctx, stream, f), "wait_frame")
 
     def set_schedule(self, kernels=capi.KERNELS_AUTO, chunk_log2=0, lanes=0, fuse_camera=capi.FUSE_AUTO, serial=False):
@@ -228,6 +277,94 @@ class HipRenderer:
         self._check(self.lib.pbr_hip_intersect(self.ctx, r.shape[0], capi.fptr(r), capi.fptr(out), int(any_hit)),
                     "intersect")
         return out
+
+
+class ProgressiveRender:
+    """A render that proceeds in sample passes and can stop, show, checkpoint and resume.
+
+    Owns the accumulator of HipRenderer.render_passes as a torch tensor on the renderer's device
+    ([n_pixels, 6] float32 in the descriptor's packed tile order: Σ Li.rgb, Σ Li.rgb²).  The image
+    after k samples is the bits of a whole render whose sampler's first k samples are these; at
+    rdesc.spp samples it is HipRenderer.render's."""
+
+    def __init__(self, renderer: HipRenderer, rdesc, device=None):
+        if rdesc.sampler == capi.SAMPLER_TABLE:
+            raise ValueError("ProgressiveRender: no passes over a sample table")
+        if rdesc.spp < 1:
+            raise ValueError("ProgressiveRender: rdesc.spp (the sample budget) must be >= 1")
+        self.renderer = renderer
+        self.rdesc = rdesc
+        self.budget = HipRenderer.sample_budget(rdesc)
+        self.n_pixels = HipRenderer.n_pixels(rdesc)
+        self.samples_done = 0
+        self._device = device
+        self._accum = self._rgb = self._rgba = self._stream = None
+
+    def _check_step(self, n_samples, passes):
+        n_samples, passes = int(n_samples), int(passes)
+        if n_samples < 1 or passes < 1:
+            raise ValueError("ProgressiveRender.step: n_samples and passes must be >= 1")
+        if self.samples_done + n_samples * passes > self.budget:
+            raise ValueError(f"ProgressiveRender.step: {self.samples_done} samples done, {n_samples * passes} more run "
+                             f"past the budget of {self.budget}")
+        return n_samples, passes
+
+    def _buffers(self):
+        import torch
+        if self._accum is None:
+            dev = self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            self._accum = torch.zeros((self.n_pixels, 6), dtype=torch.float32, device=dev)
+            self._rgb = torch.empty((self.n_pixels, 3), dtype=torch.float32, device=dev)
+            self._rgba = torch.empty((self.n_pixels, 4), dtype=torch.uint8, device=dev)
+            # the passes run on a stream of their own (the library takes a real stream handle; torch's
+            # default stream has none), ordered against the caller's current stream by events
+            self._stream = torch.cuda.Stream(dev)
+        return torch
+
+    def step(self, n_samples, passes=1):
+        """`passes` passes of n_samples samples per pixel in one call; returns the (rgb, rgba) device
+        tensors of the image after the last one.  They are reused by the next step.  Asynchronous: the
+        call returns once the passes are enqueued, and the current torch stream is made to wait for them,
+        so work queued on it afterwards (a copy to the host, a display kernel) sees the finished image."""
+        n_samples, passes = self._check_step(n_samples, passes)
+        torch = self._buffers()
+        current = torch.cuda.current_stream(self._accum.device)
+        self._stream.wait_stream(current)   # (the accumulator's initialisation or restore, readers of the last image)
+        rgb = [None] * (passes - 1) + [self._rgb.data_ptr()]
+        rgba = [None] * (passes - 1) + [self._rgba.data_ptr()]
+        self.renderer.render_passes(self.rdesc, self.samples_done, n_samples, self._accum.data_ptr(), rgb, rgba,
+                                    stream=self._stream.cuda_stream)
+        current.wait_stream(self._stream)
+        self.samples_done += n_samples * passes
+        return self._rgb, self._rgba
+
+    def variance(self):
+        """Per-pixel, per-channel sample variance [n_pixels, 3] (device tensor) from the two carried
+        sums: (Σ L² − (Σ L)²/k) / (k − 1).  An estimate: float32 sums of squares lose low bits the
+        exact variance would keep, so tiny negative values are clamped to zero."""
+        if self.samples_done < 2:
+            raise ValueError("ProgressiveRender.variance needs at least 2 samples per pixel")
+        torch = self._buffers()
+        k = float(self.samples_done)
+        s, s2 = self._accum[:, :3], self._accum[:, 3:]
+        return torch.clamp((s2 - s * s / k) / (k - 1.0), min=0.0)
+
+    def state(self) -> dict:
+        """A checkpoint: the accumulator as a numpy array and the samples done (waits for the device)."""
+        self._buffers()
+        return {"samples_done": self.samples_done, "accum": self._accum.cpu().numpy().copy()}
+
+    def restore(self, state: dict):
+        """Resume from state(): the same descriptor on any renderer holding the same scene."""
+        acc = np.asarray(state["accum"], dtype=np.float32)
+        done = int(state["samples_done"])
+        if acc.shape != (self.n_pixels, 6):
+            raise ValueError(f"ProgressiveRender.restore: accumulator of shape {acc.shape}, expected {(self.n_pixels, 6)}")
+        if done < 0 or done > self.budget:
+            raise ValueError(f"ProgressiveRender.restore: {done} samples done outside the budget of {self.budget}")
+        torch = self._buffers()
+        self._accum.copy_(torch.from_numpy(np.ascontiguousarray(acc)))
+        self.samples_done = done
 
 
 # Edge of the multi-GPU tiles.  Per-rank frame of an 8-GPU C2 job (slowest of 8 ranks, one GPU,

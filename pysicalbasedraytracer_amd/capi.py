@@ -238,6 +238,8 @@ EXPORTS = {
     "pbr_hip_render_frames": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p)]),
     "pbr_hip_wait_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "pbr_hip_render_passes": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "pbr_hip_get_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int)]),
     "pbr_hip_sampler_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -275,7 +277,7 @@ _lib = None
 OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile", "pbr_hip_query", "pbr_hip_bounds",
                    "pbr_hip_li", "pbr_hip_set_bvh_build", "pbr_hip_bvh_build_info", "pbr_hip_build_bvh",
                    "pbr_hip_set_schedule", "pbr_hip_sample_index", "pbr_hip_sample_dimensions",
-                   "pbr_hip_render_frames", "pbr_hip_wait_frame")
+                   "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -222,7 +223,11 @@ struct KParams {
     int nTiles;
     float* rgbOut;
     uint8_t* rgbaOut;
-    unsigned long long* stats; // rays, nodes, prims, shading
+    // a sample pass collects no stats: its accumulator shares the word (the block keeps its layout)
+    union {
+        unsigned long long* stats; // rays, nodes, prims, shading
+        float* accum;              // sample pass: Σ Li.rgb, Σ (Li.rgb)² per packed pixel (6 floats)
+    };
 };
 
 // GetCameraSample (Sampler.cpp:10-21) + GenerateRay: pFilm = dims 0,1; time = dim 2 (no motion
@@ -565,8 +570,7 @@ __device__ __forceinline__ void pixel_xy(const KParams& P, long long q, int* x, 
 }
 
 // Output transform (Integrator.cpp:313-344): average, XYZ round trip, sRGB gamma, 8-bit.
-__device__ __forceinline__ void film_out(const KParams& P, long long q, rgb col) {
-    col = col / (float)P.spp;
+__device__ __forceinline__ void film_write(const KParams& P, long long q, rgb col) {
     if (P.rgbOut) { P.rgbOut[3 * q] = col.r; P.rgbOut[3 * q + 1] = col.g; P.rgbOut[3 * q + 2] = col.b; }
     if (P.rgbaOut) {
         float X = 0.412453f * col.r + 0.357580f * col.g + 0.180423f * col.b;
@@ -586,9 +590,24 @@ __device__ __forceinline__ void film_out(const KParams& P, long long q, rgb col)
         reinterpret_cast<uint32_t*>(P.rgbaOut)[q] = packed;
     }
 }
+__device__ __forceinline__ void film_out(const KParams& P, long long q, rgb col) { film_write(P, q, col / (float)P.spp); }
 
-template <int INTEGRATOR, bool STATS, int OCC>
+// A sample pass (pbr_hip_render_passes): P.spp samples of every pixel, numbered from
+// P.smp.passFirst, continue the pixel's carried sums in P.accum — Σ Li and Σ Li² per channel, the same
+// in-order float additions as a whole frame's — and the image is the sum over the samples done so far.
+__device__ __forceinline__ float pass_load(const KParams& P, long long q, int c) {
+    return P.smp.passFirst > 0 ? P.accum[6 * q + c] : 0.f;   // (the first pass does not read accum)
+}
+__device__ __forceinline__ void pass_film(const KParams& P, long long q, rgb sum, rgb sum2) {
+    float* a = P.accum + 6 * q;
+    a[0] = sum.r; a[1] = sum.g; a[2] = sum.b;
+    a[3] = sum2.r; a[4] = sum2.g; a[5] = sum2.b;
+    film_write(P, q, sum / (float)(P.smp.passFirst + P.spp));
+}
+
+template <int INTEGRATOR, bool STATS, int OCC, bool PASS = false>
 __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
+    static_assert(!(PASS && STATS), "a sample pass collects no stats (accum shares their word)");
     __shared__ float lds[256 * 3];
     const int tid = threadIdx.x;
     const long long pixBase = (long long)blockIdx.x * P.ppb;
@@ -598,7 +617,14 @@ __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
     const int spp = P.spp;
     const int total = npix * spp;
     Counters cnt = {0, 0, 0, 0};
-    rgb acc = sp(0.0f);
+    rgb acc = sp(0.0f), acc2 = sp(0.0f);
+    if constexpr (PASS) {
+        if (tid < npix) {
+            const long long q = pixBase + tid;
+            acc = sp3(pass_load(P, q, 0), pass_load(P, q, 1), pass_load(P, q, 2));
+            acc2 = sp3(pass_load(P, q, 3), pass_load(P, q, 4), pass_load(P, q, 5));
+        }
+    }
     for (int base = 0; base < total; base += 256) {
         int slot = base + tid;
         rgb L = sp(0.f);
@@ -608,8 +634,9 @@ __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
             pixel_xy(P, pixBase + lp, &x, &y);
             // GlobalSampler::StartPixel/SetSampleNumber (Sampler.cpp:97-130)
             SState st;
-            st.index = sample_index(P.smp, x, y, s).lo;
-            st.sid = s;
+            const int sn = PASS ? P.smp.passFirst + s : s;   // the sample's number in the pixel
+            st.index = sample_index(P.smp, x, y, sn).lo;
+            st.sid = sn;
             st.dim = 0;
             st.px = x;
             st.py = y;
@@ -626,12 +653,15 @@ __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
             int hi = (tid + 1) * spp < base + 256 ? (tid + 1) * spp : base + 256;
             for (int k = lo; k < hi; ++k) {
                 int j = k - base;
-                acc = acc + sp3(lds[3 * j], lds[3 * j + 1], lds[3 * j + 2]);
+                const rgb Ls = sp3(lds[3 * j], lds[3 * j + 1], lds[3 * j + 2]);
+                acc = acc + Ls;
+                if constexpr (PASS) acc2 = acc2 + Ls * Ls;
             }
         }
         __syncthreads();
     }
-    if (tid < npix) film_out(P, pixBase + tid, acc);
+    if constexpr (PASS) { if (tid < npix) pass_film(P, pixBase + tid, acc, acc2); }
+    else if (tid < npix) film_out(P, pixBase + tid, acc);
     if (STATS) {
         atomicAdd(&P.stats[0], (unsigned long long)cnt.rays);
         atomicAdd(&P.stats[1], (unsigned long long)cnt.nodes);
@@ -863,6 +893,10 @@ struct pbr_hip_ctx {
     std::vector<uint32_t> sobolBuiltin;
     uint64_t sobolKey = 0;               // FNV-1a of the matrices dSobol was built from
     int sobolSrcDims = 0, sobolPixM = -1;
+    // sample passes over wide Sobol indices (sobol_pass_table): host copies of the nibble tables, and
+    // per value of the index bits >= 32 the low tables with that value's contribution folded in
+    std::vector<uint32_t> sobolNib, sobolNibHi;
+    std::map<uint32_t, std::unique_ptr<DevBuf>> sobolFold;
     DevBuf dTiles, dTileStart, dRgb, dRgba, dStats, dScratchIn, dScratchOut;
     DevBuf dTable;                       // PBR_SAMPLER_TABLE values of the current frame
     std::vector<int32_t> tilesHost;      // what dTiles / dTileStart hold (re-uploaded on change only)
@@ -882,6 +916,7 @@ struct pbr_hip_ctx {
     };
     std::vector<FrameEv> frameEv;        // (pbr_hip_wait_frame)
     int batchFrames = 0;                 // frames of the last batch
+    hipEvent_t evPass[kWfLanes] = {};    // sample passes rotating over the lanes: chunk c's last finish (pass_order)
     // Whitted: per lane, a stream for the shadow rays and per-level events (shade done, shadow done)
     hipStream_t shadowStream[kWfLanes] = {};
     hipEvent_t evShade[kWfLanes][kWfMaxDepth + 2] = {}, evShadow[kWfLanes][kWfMaxDepth + 2] = {};
@@ -1061,6 +1096,9 @@ int prepare_sobol(pbr_hip_ctx* ctx, const uint32_t* user, int userDims, int w, i
         HIP_TRY(ctx->dSobol.upload(nib, ctx->stream));
         HIP_TRY(ctx->dSobolHi.upload(nibHi, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ctx->sobolFold.clear();   // (drained above: no frame reads them)
+        ctx->sobolNib.swap(nib);
+        ctx->sobolNibHi.swap(nibHi);
         ctx->sobolKey = key;
         ctx->sobolSrcDims = dims;
         ctx->sobolPixM = -1;
@@ -1086,6 +1124,35 @@ int prepare_sobol(pbr_hip_ctx* ctx, const uint32_t* user, int userDims, int w, i
     s->sobolLog2Res = m;
     s->sobolRes = res;
     s->sobolPix = (const uint32_t*)ctx->dSobolPix.p;
+    return PBR_OK;
+}
+
+// A sample pass over wide Sobol indices in the wavefront schedules.  A sample's index bits >= 32 are its
+// number >> hiShift, which the shade kernels take from the sample's id — pixel-major over the whole
+// frame's samples, so id mod spp is the number; a pass's ids are pixel-major over the pass's samples.
+// But a pass whose samples all have the same high bits `hi` needs no per-sample value: a Sobol value
+// is the XOR of one entry from each nibble table of its dimension (sobol_nibbles, sobol_nibbles_hi), so
+// the high tables' entries for `hi` are XORed into all 16 entries of the dimension's first low table,
+// and the pass runs the unchanged kernels on that table with wideIndex off.  Built once per value
+// and kept until the matrices change; *out = the device table (hi == 0: the plain one).
+int sobol_pass_table(pbr_hip_ctx* ctx, uint32_t hi, const uint32_t** out) {
+    *out = (const uint32_t*)ctx->dSobol.p;
+    if (hi == 0) return PBR_OK;
+    std::unique_ptr<DevBuf>& buf = ctx->sobolFold[hi];
+    if (!buf) {
+        std::vector<uint32_t> t = ctx->sobolNib;
+        const int dims = ctx->sobolSrcDims;
+        for (int d = 0; d < dims; ++d) {
+            uint32_t h = 0;
+            for (int k = 0; k < 5; ++k) h ^= ctx->sobolNibHi[(size_t)d * kSobolNibHi + 16 * k + ((hi >> (4 * k)) & 15u)];
+            for (int n = 0; n < 16; ++n) t[(size_t)d * kSobolNib + n] ^= h;
+        }
+        auto fresh = std::make_unique<DevBuf>();
+        HIP_TRY(fresh->upload(t, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));   // the host vector dies on return
+        buf = std::move(fresh);
+    }
+    *out = (const uint32_t*)buf->p;
     return PBR_OK;
 }
 
@@ -1204,7 +1271,23 @@ struct FrameSet {
     float* const* rgb = nullptr;     // per frame (batch); the single frame's outputs are in KParams
     uint8_t* const* rgba = nullptr;
     bool batch = false;
+    // sample passes (pbr_hip_render_passes): frame f draws samples [first + f·P.spp, first + (f+1)·P.spp)
+    // of every pixel onto the carried sums in `accum` (KParams::spp is the pass's count)
+    float* accum = nullptr;
+    int first = 0, passSpp = 0;
+    std::vector<const uint32_t*> sobolPass;   // wide Sobol indices: pass f's table (sobol_pass_table), else empty
 };
+// Passes share `accum`: pass p+1's finish over a pixel range reads what pass p's finish over that
+// range wrote.  Passes of several chunks fork and join per pass, which orders them; passes that
+// continue one rotation over the lanes (fewer chunks than lanes) run chunk c of consecutive passes on
+// different lanes, so each finish waits for the event recorded after the one before it on chunk c.
+int pass_order(pbr_hip_ctx* ctx, hipStream_t st, int c, bool wait) {
+    hipEvent_t& e = ctx->evPass[c];
+    if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (wait) HIP_TRY(hipStreamWaitEvent(st, e, 0));
+    else HIP_TRY(hipEventRecord(e, st));
+    return PBR_OK;
+}
 // Lanes and hardware queues (PBR_OWN_LANES).  HIP gives a process a few hardware queues (4 by
 // default) and deals them to streams in creation order, so lanes only run side by side when their
 // streams hold different queues.  The context creates its stream and the lane streams 1-3 together
@@ -1403,6 +1486,7 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
         W.P.smp.ldsDims = std::min(kLdsDims, 5 + (2 * lightsPerShade + 2) * levels + 2);
         W.cap = (int)cap;
     }
+    const bool pass = F.accum != nullptr;
     auto queue = [&](int l, int k) {
         WfBufs& B = ctx->wb[l];
         WfQueue q;
@@ -1438,6 +1522,8 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
             W.P.rgbaOut = F.rgba ? F.rgba[f] : nullptr;
             used |= 1u << l;
         }
+        if (pass) W.P.smp.passFirst = F.first + f * spp;
+        if (!F.sobolPass.empty()) { W.P.smp.sobol = F.sobolPass[f]; W.P.smp.wideIndex = 0; }
         W.chunkPix0 = p0;
         W.chunkPix = (int)std::min<long long>(ch.chunkPix, P.nPixels - p0);
         W.nSamples = W.chunkPix * spp;
@@ -1445,7 +1531,8 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
         W.cur = queue(l, 0);
         if (!fuseCamera) {
             PROF_LAUNCH(KP_WF_CAMERA, st,
-                hipLaunchKernelGGL(k_wf_camera_extend<kCameraShort>, dim3((W.nSamples + 255) / 256), blk, 0, st, W));
+                if (pass) hipLaunchKernelGGL((k_wf_camera_extend<kCameraShort, true>), dim3((W.nSamples + 255) / 256), blk, 0, st, W);
+                else hipLaunchKernelGGL(k_wf_camera_extend<kCameraShort>, dim3((W.nSamples + 255) / 256), blk, 0, st, W));
         }
         prof_host(ctx, KP_WF_CAMERA, 0, (unsigned long long)W.nSamples);
         const hipStream_t sst = shadowOverlap ? ctx->shadowStream[l] : st;
@@ -1473,6 +1560,10 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
                 else if (simple) hipLaunchKernelGGL((k_wf_shade_ml<kSimpleLobes, false>), gstride, blk, 0, st, W, l0);
                 else if (matsLds) hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes, true>), gstride, blk, 0, st, W, l0);
                 else hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes, false>), gstride, blk, 0, st, W, l0);
+            } else if (fuseCamera && l0 && pass) {   // the fused level 0 of a sample pass
+                if (mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true, true>), gstride, blk, 0, st, W, l0);
+                else if (mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0);
+                else hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0);
             } else if (fuseCamera && l0 && mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true>), gstride, blk, 0, st, W, l0);
             else if (fuseCamera && l0 && mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0);
             else if (fuseCamera && l0) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0);
@@ -1505,7 +1596,12 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
         // the fold reads every level's records: after the last shadow launch (stream order on sst)
         if (shadowOverlap) HIP_TRY(hipStreamWaitEvent(st, ctx->evShadow[l][maxLevels - 1], 0));
         const int pb = finish_pixels(spp);
-        PROF_LAUNCH(KP_WF_FINISH, st, hipLaunchKernelGGL(k_wf_finish<0>, dim3((W.chunkPix + pb - 1) / pb), blk, 0, st, W));
+        const bool ordered = pass && rotate;   // (pass_order)
+        if (ordered && f > 0) { if (int rc = pass_order(ctx, st, chunk % (int)nChunks, true)) return rc; }
+        PROF_LAUNCH(KP_WF_FINISH, st,
+            if (pass) hipLaunchKernelGGL(k_wf_finish<1>, dim3((W.chunkPix + pb - 1) / pb), blk, 0, st, W);
+            else hipLaunchKernelGGL(k_wf_finish<0>, dim3((W.chunkPix + pb - 1) / pb), blk, 0, st, W));
+        if (ordered) { if (int rc = pass_order(ctx, st, chunk % (int)nChunks, false)) return rc; }
         prof_host(ctx, KP_WF_FINISH, 0, (unsigned long long)W.chunkPix);
         prof_host(ctx, KP_WF_FINISH, 1, (unsigned long long)W.nSamples);
     }
@@ -1637,6 +1733,7 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
         // Path: 5 camera dims + per bounce 1 + 2 + 2 (light) + 2 (BSDF) + 1 (RR)
         W.P.smp.ldsDims = std::min(kLdsDims, 5 + 8 * std::max(1, P.maxDepth) + 2);
     }
+    const bool pass = F.accum != nullptr;
     auto queue = [&](int l, int k) {
         WfBufs& B = ctx->wb[l];
         WfQueue q;
@@ -1680,12 +1777,16 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
             W.P.rgbaOut = F.rgba ? F.rgba[f] : nullptr;
             used |= 1u << l;
         }
+        if (pass) W.P.smp.passFirst = F.first + f * spp;
+        if (!F.sobolPass.empty()) { W.P.smp.sobol = F.sobolPass[f]; W.P.smp.wideIndex = 0; }
         W.chunkPix0 = p0;
         W.chunkPix = (int)std::min<long long>(ch.chunkPix, P.nPixels - p0);
         W.nSamples = W.chunkPix * spp;
         int cur = 0;
         W.cur = queue(l, 0);
-        PROF_LAUNCH(KP_WFP_CAMERA, st, hipLaunchKernelGGL(k_wfp_camera_extend<kCameraShort>, dim3((W.nSamples + 255) / 256), blk, 0, st, X));
+        PROF_LAUNCH(KP_WFP_CAMERA, st,
+            if (pass) hipLaunchKernelGGL((k_wfp_camera_extend<kCameraShort, true>), dim3((W.nSamples + 255) / 256), blk, 0, st, X);
+            else hipLaunchKernelGGL(k_wfp_camera_extend<kCameraShort>, dim3((W.nSamples + 255) / 256), blk, 0, st, X));
         prof_host(ctx, KP_WFP_CAMERA, 0, (unsigned long long)W.nSamples);
         for (int level = 0;; ++level) {   // ends below: at maxLevels, or when no continuation is queued
             W.cur = queue(l, cur);
@@ -1770,7 +1871,12 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
             if (int rc = prof_sums(ctx, st, KP_WF_EXTEND, {W.cur.segCount})) return rc;
         }
         const int pb = finish_pixels(spp);
-        PROF_LAUNCH(KP_WFP_FINISH, st, hipLaunchKernelGGL(k_wfp_finish, dim3((W.chunkPix + pb - 1) / pb), blk, 0, st, X));
+        const bool ordered = pass && rotate;   // (pass_order)
+        if (ordered && f > 0) { if (int rc = pass_order(ctx, st, chunk % (int)nChunks, true)) return rc; }
+        PROF_LAUNCH(KP_WFP_FINISH, st,
+            if (pass) hipLaunchKernelGGL(k_wfp_finish_pass, dim3((W.chunkPix + pb - 1) / pb), blk, 0, st, X);
+            else hipLaunchKernelGGL(k_wfp_finish, dim3((W.chunkPix + pb - 1) / pb), blk, 0, st, X));
+        if (ordered) { if (int rc = pass_order(ctx, st, chunk % (int)nChunks, false)) return rc; }
         prof_host(ctx, KP_WFP_FINISH, 0, (unsigned long long)W.chunkPix);
         prof_host(ctx, KP_WFP_FINISH, 1, (unsigned long long)W.nSamples);
     }
@@ -2040,6 +2146,7 @@ int pbr_hip_destroy(pbr_hip_ctx* ctx) {
             if (e.ev[l]) (void)hipEventDestroy(e.ev[l]);
     for (int l = 0; l < kWfLanes; ++l) {
         if (ctx->evJoin[l]) (void)hipEventDestroy(ctx->evJoin[l]);
+        if (ctx->evPass[l]) (void)hipEventDestroy(ctx->evPass[l]);
         if (ctx->side[l]) (void)hipStreamDestroy(ctx->side[l]);
     }
     for (auto& e : ctx->profEv) {
@@ -2145,12 +2252,13 @@ int pbr_hip_upload_scene(pbr_hip_ctx* ctx, const pbr_scene_desc* desc) {
 }
 
 static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_out, uint8_t* rgba_out, pbr_render_stats* stats,
-                       const FrameSet& F) {
+                       FrameSet F) {
     if (!ctx) return PBR_E_INVALID;
     if (!d) return set_err(ctx, PBR_E_INVALID, "null render desc");
     if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
     if (F.batch && (!d->outputs_on_device || d->collect_stats || stats || d->sampler == PBR_SAMPLER_TABLE || F.n < 1))
-        return set_err(ctx, PBR_E_INVALID, "render_frames: device outputs, no stats, no sample table, n >= 1");
+        return set_err(ctx, PBR_E_INVALID, std::string(F.accum ? "render_passes" : "render_frames") +
+                                               ": device outputs, no stats, no sample table, n >= 1");
     if (F.batch) ctx->batchFrames = 0;   // (set when the batch is queued)
     auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2166,6 +2274,33 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
     hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
     KParams P;
     if (int rc = make_params(ctx, d, &P)) return rc;
+    if (F.accum) {   // sample passes: P.spp is the sampler's budget (Sobol: rounded up) until here
+        if ((long long)F.first + (long long)F.n * F.passSpp > (long long)P.spp)
+            return set_err(ctx, PBR_E_INVALID, "render_passes: samples [" + std::to_string(F.first) + ", " +
+                           std::to_string((long long)F.first + (long long)F.n * F.passSpp) + ") run past the budget of " +
+                           std::to_string(P.spp) + " samples per pixel");
+        P.spp = F.passSpp;
+        P.ppb = P.spp >= 256 ? 1 : 256 / P.spp;
+        P.smp.passFirst = F.first;
+        P.accum = F.accum;
+    }
+    // Wide Sobol indices: passes whose samples each share their index bits >= 32 run the wavefront
+    // kernels on folded tables (sobol_pass_table); a call with a pass that straddles two values runs the
+    // megakernel, which numbers its samples itself.
+    bool passMega = false;
+    if (F.accum && P.smp.wideIndex) {
+        std::vector<uint32_t> hi(F.n);
+        for (int f = 0; f < F.n; ++f) {
+            const uint32_t a = (uint32_t)(F.first + f * F.passSpp), b = a + (uint32_t)F.passSpp - 1u;
+            hi[f] = a >> P.smp.hiShift;
+            if ((b >> P.smp.hiShift) != hi[f]) passMega = true;
+        }
+        if (!passMega) {
+            F.sobolPass.resize(F.n);
+            for (int f = 0; f < F.n; ++f)
+                if (int rc = sobol_pass_table(ctx, hi[f], &F.sobolPass[f])) return rc;
+        }
+    }
     const int spp = P.spp;
     // tiles
     std::vector<int32_t> tiles;
@@ -2223,7 +2358,7 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
     if (blocks > 0) {
         bool st = d->collect_stats != 0;
         // (a tree too deep for the quad walk's stack runs the megakernel's binary walk)
-        const bool mega = ctx->sched.kernels == PBR_KERNELS_MEGAKERNEL || ctx->host.quadStackNeed > kQuadStackLimit;
+        const bool mega = ctx->sched.kernels == PBR_KERNELS_MEGAKERNEL || ctx->host.quadStackNeed > kQuadStackLimit || passMega;
         // Whitted through material-less primitives recurses at the same depth without bound
         // (WhittedIntegrator.cpp:26-28): only the megakernel follows such chains to the end
         bool wavefront = d->integrator == PBR_INTEGRATOR_WHITTED && !st && ctx->host.lights.size() <= (size_t)kWfMaxLightsML &&
@@ -2234,7 +2369,8 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
         // the megakernel at 2 waves per SIMD (it trades VGPRs for scratch): 2 beat 1 by 1.78x on C2
         // and tied 4
 #define PBR_LAUNCH(I)                                                                                 \
-    if (st) hipLaunchKernelGGL((k_render<I, true, 1>), grid, block, 0, s, P);                        \
+    if (F.accum) hipLaunchKernelGGL((k_render<I, false, 2, true>), grid, block, 0, s, P);            \
+    else if (st) hipLaunchKernelGGL((k_render<I, true, 1>), grid, block, 0, s, P);                   \
     else hipLaunchKernelGGL((k_render<I, false, 2>), grid, block, 0, s, P);
         if (wavefront || wavefrontPath) {
             int rc = wavefront ? render_wavefront(ctx, P, s, F) : render_wavefront_path(ctx, P, s, d->integrator == PBR_INTEGRATOR_VOLPATH, F);
@@ -2248,6 +2384,7 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
                     P.rgbOut = F.rgb ? F.rgb[f] : nullptr;
                     P.rgbaOut = F.rgba ? F.rgba[f] : nullptr;
                 }
+                if (F.accum) P.smp.passFirst = F.first + f * spp;   // (passes on `s`: in order)
                 PROF_LAUNCH(KP_MEGA, s,
                     switch (d->integrator) {
                     case PBR_INTEGRATOR_WHITTED: PBR_LAUNCH(PBR_INTEGRATOR_WHITTED) break;
@@ -2314,6 +2451,26 @@ int pbr_hip_render_frames(pbr_hip_ctx* ctx, const pbr_render_desc* d, int n, flo
     F.rgb = rgb_outs;
     F.rgba = rgba_outs;
     F.batch = true;
+    return render_impl(ctx, d, nullptr, nullptr, nullptr, F);
+}
+
+int pbr_hip_render_passes(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sample, int samples_per_pass, int n_passes,
+                          float* accum, float* const* rgb_outs, uint8_t* const* rgba_outs) {
+    if (!ctx) return PBR_E_INVALID;
+    if (!d) return set_err(ctx, PBR_E_INVALID, "render_passes: null render desc");
+    if (!accum) return set_err(ctx, PBR_E_INVALID, "render_passes: accum must be a device buffer of 6 floats per pixel");
+    if (samples_per_pass < 1) return set_err(ctx, PBR_E_INVALID, "render_passes: samples_per_pass must be >= 1");
+    if (n_passes < 1) return set_err(ctx, PBR_E_INVALID, "render_passes: n_passes must be >= 1");
+    if (first_sample < 0) return set_err(ctx, PBR_E_INVALID, "render_passes: first_sample must be >= 0");
+    if (d->sampler == PBR_SAMPLER_TABLE) return set_err(ctx, PBR_E_UNSUPPORTED, "render_passes: no passes over a sample table");
+    FrameSet F;
+    F.n = n_passes;
+    F.rgb = rgb_outs;
+    F.rgba = rgba_outs;
+    F.batch = true;
+    F.accum = accum;
+    F.first = first_sample;
+    F.passSpp = samples_per_pass;
     return render_impl(ctx, d, nullptr, nullptr, nullptr, F);
 }
 

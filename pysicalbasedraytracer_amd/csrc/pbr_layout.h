@@ -144,7 +144,10 @@ struct DeviceSampler {
     int ldsDims;                   // Halton dimensions a kernel may stage in LDS (<= 64)
     // PBR_SAMPLER_TABLE: the caller's values, [((y * tableW + x) * spp + s) * tableDims + dim]
     const float* table;
-    int tableDims, tableW;
+    int tableDims;
+    // A sample pass (pbr_hip_render_passes) has no table, so the number of its first sample shares a
+    // word of the table's: the parameter block of every kernel keeps its size and layout.
+    union { int tableW; int passFirst; };
     int* guard;                    // DeviceScene::guard: a dimension beyond the table fails the frame
 };
 

@@ -430,7 +430,9 @@ __device__ void traverse_stream(const DeviceScene& S, int n, int segCap, Load lo
 #endif
 }
 
-template <int SHORT>
+// PASS (here and in the kernels below): a sample pass — sample s of the pass is sample number
+// passFirst + s of the pixel (pass_film, pbr_kernels.hip)
+template <int SHORT, bool PASS = false>
 __global__ __launch_bounds__(256, PBR_TRAV_OCC) void k_wf_camera_extend(WfParams W) {
     const KParams& P = W.P;
     int q = wf_block() * blockDim.x + threadIdx.x;
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(256, PBR_TRAV_OCC) void k_wf_camera_extend(WfParams
     int x, y;
     pixel_xy(P, W.chunkPix0 + lp, &x, &y);
     SState st;
-    st.index = sample_index(P.smp, x, y, s).lo;
+    st.index = sample_index(P.smp, x, y, PASS ? P.smp.passFirst + s : s).lo;
     st.sid = s;
     st.dim = 0;
     st.px = x;
@@ -545,7 +547,7 @@ __shared__ MatTemplate s_mats[kLdsMats];
 // k_wf_camera_extend's work for queue position q inside the level-0 shade (CAMERA): the camera
 // sample's ray and its closest hit, as the queue entry the shade would have read.  Every lane of
 // the wave calls it (the packet walk is wave-wide); `active` lanes hold a sample.
-template <bool PINHOLE = false, int KIND = -1>
+template <bool PINHOLE = false, int KIND = -1, bool PASS = false>
 __device__ __forceinline__ void camera_trace(const WfParams& W, bool active, int q, float4* o, float4* d, float4* hr,
                                              uint32_t* index) {
     const KParams& P = W.P;
@@ -557,7 +559,7 @@ __device__ __forceinline__ void camera_trace(const WfParams& W, bool active, int
         int x, y;
         pixel_xy(P, W.chunkPix0 + lp, &x, &y);
         SState st;
-        st.index = sample_index<KIND>(P.smp, x, y, s).lo;
+        st.index = sample_index<KIND>(P.smp, x, y, PASS ? P.smp.passFirst + s : s).lo;
         st.sid = s;
         st.dim = 0;
         st.px = x;
@@ -593,8 +595,9 @@ __device__ __forceinline__ void camera_trace(const WfParams& W, bool active, int
 // material make_bsdf accepts, with a non-specular lobe.
 template <int LOBES, bool MATS_LDS,
           int OCC = (LOBES & ~kSimpleLobes) ? 2 : (LOBES == kMatteMirrorLobes ? PBR_WF_SHADE_OCC_MM : PBR_WF_SHADE_OCC),
-          bool CAMERA = false, bool SKY = false>
+          bool CAMERA = false, bool SKY = false, bool PASS = false>
 __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0) {
+    static_assert(!PASS || CAMERA, "only the fused level-0 shade starts samples");
     static_assert(!SKY || (LOBES & kTexturedLobes) == 0, "the SkyBox variant is untextured");
     constexpr int kSmp = SKY ? PBR_SAMPLER_HALTON : -1;   // the SkyBox variants run Halton frames only
     const KParams& P = W.P;
@@ -626,7 +629,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0) {
         f3 skyWi = mk(0, 0, 0);
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f), d = o, hr = o;
         uint32_t camIndex = 0;
-        if constexpr (CAMERA) camera_trace<SKY, kSmp>(W, active, q, &o, &d, &hr, &camIndex);   // level 0 only
+        if constexpr (CAMERA) camera_trace<SKY, kSmp, PASS>(W, active, q, &o, &d, &hr, &camIndex);   // level 0 only
         else if (active) { o = W.cur.o[q]; d = W.cur.d[q]; hr = W.cur.hit[q]; }
         if (active) {
             id = level0 ? q : W.cur.id[q];
@@ -1012,14 +1015,30 @@ __device__ __forceinline__ rgb level_direct(const WfParams& W, int lv, int id, f
 }
 
 constexpr int kFinishSamples = 2048;
+// The end of the finish kernels: thread t < 3·npx holds channel t%3 of pixel t/3's sum (a pass: and
+// of its sum of squares); thread p < npx writes pixel p.  `sum`: 64·3 floats of LDS (a pass: twice).
+template <bool PASS>
+__device__ __forceinline__ void finish_film(const KParams& P, long long q0, int npx, float* sum, float acc, float acc2) {
+    if ((int)threadIdx.x < 3 * npx) {
+        sum[threadIdx.x] = acc;
+        if constexpr (PASS) sum[64 * 3 + threadIdx.x] = acc2;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < npx) {
+        const float* a = sum + 3 * threadIdx.x;
+        if constexpr (PASS) pass_film(P, q0 + threadIdx.x, sp3(a[0], a[1], a[2]), sp3(a[64 * 3], a[64 * 3 + 1], a[64 * 3 + 2]));
+        else film_out(P, q0 + threadIdx.x, sp3(a[0], a[1], a[2]));
+    }
+}
 __host__ __device__ inline int finish_pixels(int spp) {
     int pb = kFinishSamples / spp;
     return pb < 1 ? 1 : (pb > 64 ? 64 : pb);
 }
-template <int DUMMY>
+// PASS = 1: a sample pass — the sums continue the pixel's carried ones, and Σ L² is carried with them
+template <int PASS>
 __global__ __launch_bounds__(256) void k_wf_finish(WfParams W) {
     __shared__ float lds[3 * (kFinishSamples + 64)];
-    __shared__ float sum[64 * 3];
+    __shared__ float sum[64 * 3 * (PASS != 0 ? 2 : 1)];
     const KParams& P = W.P;
     const int spp = P.spp, pitch = min(spp, kFinishSamples) + 1;
     const int pb = finish_pixels(spp);
@@ -1028,6 +1047,14 @@ __global__ __launch_bounds__(256) void k_wf_finish(WfParams W) {
     // spp > kFinishSamples: one pixel per block, folded and summed in slices of kFinishSamples
     const int slice = min(spp, kFinishSamples);
     float acc = 0.f;   // thread t < 3·npx: channel t%3 of pixel t/3
+    float acc2 = 0.f;
+    if constexpr (PASS != 0) {
+        if ((int)threadIdx.x < 3 * npx) {
+            const long long q = W.chunkPix0 + lp0 + threadIdx.x / 3;
+            acc = pass_load(P, q, threadIdx.x % 3);
+            acc2 = pass_load(P, q, 3 + threadIdx.x % 3);
+        }
+    }
     for (int s0 = 0; s0 < spp; s0 += slice) {
         const int ns = npx * min(slice, spp - s0);
         for (int t = threadIdx.x; t < ns; t += blockDim.x) {
@@ -1052,12 +1079,12 @@ __global__ __launch_bounds__(256) void k_wf_finish(WfParams W) {
         if ((int)threadIdx.x < 3 * npx) {
             const int n = min(slice, spp - s0);
             const float* row = lds + threadIdx.x * pitch;
-            for (int k = 0; k < n; ++k) acc = acc + row[k];
+            for (int k = 0; k < n; ++k) {
+                acc = acc + row[k];
+                if constexpr (PASS != 0) acc2 = acc2 + row[k] * row[k];
+            }
         }
         __syncthreads();
     }
-    if ((int)threadIdx.x < 3 * npx) sum[threadIdx.x] = acc;
-    __syncthreads();
-    if ((int)threadIdx.x < npx)
-        film_out(P, W.chunkPix0 + lp0 + threadIdx.x, sp3(sum[3 * threadIdx.x], sum[3 * threadIdx.x + 1], sum[3 * threadIdx.x + 2]));
+    finish_film<PASS != 0>(P, W.chunkPix0 + lp0, npx, sum, acc, acc2);
 }

@@ -61,7 +61,7 @@ __device__ __forceinline__ int pack_path(int dim, int bounces, bool specular) {
     return (dim & 0xffff) | ((bounces & 0x7f) << 16) | (specular ? (1 << 23) : 0);
 }
 
-template <int SHORT>
+template <int SHORT, bool PASS = false>
 __global__ __launch_bounds__(256, PBR_TRAV_OCC) void k_wfp_camera_extend(WfpParams X) {
     WfParams& W = X.W;
     const KParams& P = W.P;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256, PBR_TRAV_OCC) void k_wfp_camera_extend(WfpPara
     int x, y;
     pixel_xy(P, W.chunkPix0 + lp, &x, &y);
     SState st;
-    st.index = sample_index(P.smp, x, y, s).lo;
+    st.index = sample_index(P.smp, x, y, PASS ? P.smp.passFirst + s : s).lo;
     st.sid = s;
     st.dim = 0;
     st.px = x;
@@ -558,17 +558,25 @@ __global__ __launch_bounds__(256) void k_wfp_resolve(WfpParams X) {
 }
 
 // Per-pixel in-order sum of the per-sample L (colObj += Li) and the film; layout as k_wf_finish.
-__global__ __launch_bounds__(256) void k_wfp_finish(WfpParams X) {
+template <bool PASS>
+__device__ __forceinline__ void wfp_finish(WfpParams& X) {
     WfParams& W = X.W;
     __shared__ float lds[3 * (kFinishSamples + 64)];
-    __shared__ float sum[64 * 3];
+    __shared__ float sum[64 * 3 * (PASS ? 2 : 1)];
     const KParams& P = W.P;
     const int spp = P.spp, pitch = min(spp, kFinishSamples) + 1;
     const int pb = finish_pixels(spp);
     const int lp0 = blockIdx.x * pb;   // dispatch order: the XCD-run order made finish 28% slower
     const int npx = min(pb, W.chunkPix - lp0);
     const int slice = min(spp, kFinishSamples);
-    float acc = 0.f;
+    float acc = 0.f, acc2 = 0.f;
+    if constexpr (PASS) {
+        if ((int)threadIdx.x < 3 * npx) {
+            const long long q = W.chunkPix0 + lp0 + threadIdx.x / 3;
+            acc = pass_load(P, q, threadIdx.x % 3);
+            acc2 = pass_load(P, q, 3 + threadIdx.x % 3);
+        }
+    }
     for (int s0 = 0; s0 < spp; s0 += slice) {
         const int ns = npx * min(slice, spp - s0);
         for (int t = threadIdx.x; t < ns; t += blockDim.x) {
@@ -583,12 +591,14 @@ __global__ __launch_bounds__(256) void k_wfp_finish(WfpParams X) {
         if ((int)threadIdx.x < 3 * npx) {
             const int cnt = min(slice, spp - s0);
             const float* row = lds + threadIdx.x * pitch;
-            for (int k = 0; k < cnt; ++k) acc = acc + row[k];
+            for (int k = 0; k < cnt; ++k) {
+                acc = acc + row[k];
+                if constexpr (PASS) acc2 = acc2 + row[k] * row[k];
+            }
         }
         __syncthreads();
     }
-    if ((int)threadIdx.x < 3 * npx) sum[threadIdx.x] = acc;
-    __syncthreads();
-    if ((int)threadIdx.x < npx)
-        film_out(P, W.chunkPix0 + lp0 + threadIdx.x, sp3(sum[3 * threadIdx.x], sum[3 * threadIdx.x + 1], sum[3 * threadIdx.x + 2]));
+    finish_film<PASS>(P, W.chunkPix0 + lp0, npx, sum, acc, acc2);
 }
+__global__ __launch_bounds__(256) void k_wfp_finish(WfpParams X) { wfp_finish<false>(X); }
+__global__ __launch_bounds__(256) void k_wfp_finish_pass(WfpParams X) { wfp_finish<true>(X); }

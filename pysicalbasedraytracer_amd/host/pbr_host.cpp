@@ -1548,6 +1548,96 @@ void AssembleTiles(const std::vector<Bounds2i>& tiles, const float* packed, int 
     assemble(tiles, packed, ch, width, frame);
 }
 
+// Device buffers of RenderSamples: 6 floats of sums, 3 floats and 4 bytes of image per pixel.
+struct SamplerIntegrator::Progressive {
+    int device = 0;
+    size_t npx = 0;
+    float* accum = nullptr;
+    float* rgb = nullptr;
+    uint8_t* rgba = nullptr;
+    ~Progressive() {
+        if (hipSetDevice(device) != hipSuccess) return;
+        if (accum) (void)hipFree(accum);
+        if (rgb) (void)hipFree(rgb);
+        if (rgba) (void)hipFree(rgba);
+    }
+};
+
+void SamplerIntegrator::RenderSamples(const Scene& scene, int firstSample, int nSamples) {
+    if (!devices.empty()) throw std::invalid_argument("RenderSamples: one device (SetDevice), not SetDevices");
+    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
+    if (!cam) throw std::invalid_argument("RenderSamples: only PerspectiveCamera is on the GPU path");
+    check_sampler(*sampler, *cam, "RenderSamples");
+    if (sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
+        throw std::invalid_argument("RenderSamples: a custom sampler's values go to the device as a whole frame's table; "
+                                    "sample passes need HaltonSampler or SobolSampler");
+    if (firstSample < 0 || nSamples < 1) throw std::invalid_argument("RenderSamples: firstSample >= 0 and nSamples >= 1");
+    if (firstSample != 0 && (!prog || firstSample != samplesDone))
+        throw std::invalid_argument("RenderSamples: firstSample " + std::to_string(firstSample) + " does not continue the " +
+                                    std::to_string(prog ? samplesDone : 0) + " samples done");
+    const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;   // the reference reads pMax only
+    if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
+        throw std::invalid_argument("RenderSamples: pixelBounds outside the camera raster");
+    ensure_scene(scene);
+    auto flat = FlattenScene(scene, cam->medium);   // for the camera medium's index
+    pbr_render_desc rd;
+    std::memset(&rd, 0, sizeof(rd));
+    rd.integrator = IntegratorType();
+    rd.max_depth = MaxDepth();
+    rd.rr_threshold = RRThreshold();
+    rd.light_strategy = LightStrategy();
+    rd.sampler = sampler->DeviceSampler();
+    rd.spp = (int)sampler->samplesPerPixel;
+    camera_desc(*cam, &rd.camera);
+    rd.camera.medium = MediumIndex(*flat, cam->medium);
+    std::vector<pbr_tile> tl;
+    if (!tiles.empty()) {
+        for (const Bounds2i& b : tiles) tl.push_back({b.pMin.x, b.pMin.y, b.pMax.x, b.pMax.y});
+    } else {
+        tl.push_back({0, 0, W, H});
+    }
+    rd.n_tiles = (int)tl.size();
+    rd.tiles = tl.data();
+    rd.outputs_on_device = 1;
+    size_t npx = 0;
+    for (const pbr_tile& t : tl) npx += (size_t)(t.x1 - t.x0) * (t.y1 - t.y0);
+    hip_check(hipSetDevice(device), "hipSetDevice");
+    if (!prog || prog->npx != npx || prog->device != device) {
+        if (firstSample != 0) throw std::invalid_argument("RenderSamples: the tiles changed since the last call");
+        prog = std::make_shared<Progressive>();
+        prog->device = device;
+        prog->npx = npx;
+        hip_check(hipMalloc((void**)&prog->accum, std::max<size_t>(1, npx) * 6 * sizeof(float)), "hipMalloc");
+        hip_check(hipMalloc((void**)&prog->rgb, std::max<size_t>(1, npx) * 3 * sizeof(float)), "hipMalloc");
+        hip_check(hipMalloc((void**)&prog->rgba, std::max<size_t>(1, npx) * 4), "hipMalloc");
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    float* rgbOut[1] = {prog->rgb};
+    uint8_t* rgbaOut[1] = {prog->rgba};
+    check(ctx, pbr_hip_render_passes(ctx, &rd, firstSample, nSamples, 1, prog->accum, rgbOut, rgbaOut), "pbr_hip_render_passes");
+    check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
+    samplesDone = firstSample + nSamples;
+    std::vector<float> rgb(npx * 3);
+    std::vector<uint8_t> rgba(npx * 4);
+    hip_check(hipMemcpy(rgb.data(), prog->rgb, rgb.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(rgba.data(), prog->rgba, rgba.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+    if (m_FrameBuffer) {
+        if (m_FrameBuffer->width != W || m_FrameBuffer->height != H || m_FrameBuffer->channals < 3)
+            throw std::invalid_argument("RenderSamples: FrameBuffer not initialised to the pixel bounds");
+        size_t k = 0;
+        for (const pbr_tile& t : tl)
+            for (int y = t.y0; y < t.y1; ++y)
+                for (int x = t.x0; x < t.x1; ++x, ++k)
+                    for (int ch = 0; ch < m_FrameBuffer->channals; ++ch) {   // (flipped, as Render: Integrator.cpp:341-344)
+                        m_FrameBuffer->set_uc(x, H - y - 1, ch, rgba[4 * k + ch]);
+                        m_FrameBuffer->set_fc(x, H - y - 1, ch, ch < 3 ? rgb[3 * k + ch] : 1.f);
+                    }
+    }
+    stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    stats.kernel_ms = 0;   // (passes are enqueued without event timing)
+    stats.samples = (uint64_t)npx * (uint64_t)nSamples;
+}
+
 struct SamplerIntegrator::MultiGPU {
     std::vector<int> devs;
     int W = 0, H = 0;
