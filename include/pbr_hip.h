@@ -415,6 +415,31 @@ int pbr_hip_sample_dimensions(pbr_hip_ctx* ctx, int sampler, int width, int heig
 int pbr_hip_camera_rays(pbr_hip_ctx* ctx, const pbr_camera_desc* cam, int n, const float* pfilm, float* out);
 /* Closest-hit queries on the device: rays = o.xyz d.xyz tmax; out = {hit, t, prim_id, b1, b2} as floats */
 int pbr_hip_intersect(pbr_hip_ctx* ctx, int n, const float* rays, float* out, int any_hit);
+/* The same queries through one of the BVH walks the render schedules run (rays and out as above;
+ * every walk returns the records pbr_hip_intersect returns).  Each value runs the walk with the
+ * template arguments and launch bounds of its production users. */
+enum pbr_walk {
+    PBR_WALK_LANE = 0,       /* what pbr_hip_intersect runs: the per-lane quad walk, private stack */
+    PBR_WALK_LANE_LDS = 1,   /* the per-lane quad walk with the LDS short stack (Whitted's shadow kernels) */
+    PBR_WALK_PACKET = 2,     /* the wave-packet walk (camera kernels; Whitted's extend when a queue is given);
+                              * closest hit only: PBR_E_UNSUPPORTED with any_hit */
+    PBR_WALK_REFILL = 3,     /* lane refill over a segmented queue: closest hit (Path's extend and probe kernels)
+                              * or any hit (Path's shadow kernel) */
+    PBR_WALK_BINARY = 4,     /* the binary walk of trees too deep for the quad walk's stack */
+    PBR_WALK_REFILL_TR = 5   /* lane refill as VolPath's transmittance kernel instantiates it; any hit only:
+                              * PBR_E_UNSUPPORTED without any_hit */
+};
+/* The queue walks (PBR_WALK_REFILL, PBR_WALK_REFILL_TR, and PBR_WALK_PACKET when seg_cap > 0 or
+ * seg_counts is given, which runs Whitted's extend kernel) lay the rays out as a segmented queue of
+ * PBR_WALK_SEGMENTS segments of seg_cap entries: seg_counts[s] rays in segment s, ray i at the i-th
+ * dense position; seg_counts = NULL fills the segments in order (the densest prefix), seg_cap = 0
+ * picks a capacity.  The other walks take seg_cap = 0 and seg_counts = NULL.  PBR_E_INVALID: an
+ * unknown walk, counts that do not sum to n or exceed seg_cap, a queue above 256 MB.
+ * PBR_E_UNSUPPORTED: a quad, packet or refill walk on a scene whose tree is walked in binary form
+ * (the quad walk's stack cannot hold it), or a walk that reached a safety bound. */
+#define PBR_WALK_SEGMENTS 2048
+int pbr_hip_intersect_walk(pbr_hip_ctx* ctx, int walk, int n, const float* rays, float* out, int any_hit,
+                           int seg_cap, const int32_t* seg_counts);
 /* ---- the reference's C++ query surface, batched (include/pbr/pbr.h builds on these) ---- */
 /* SurfaceInteraction fields of a hit (Core/Interaction.h:56-105), as GeometricPrimitive::Intersect
  * leaves them (Primitive.cpp:22-36): t = the ray's new tMax. */

@@ -1962,7 +1962,7 @@ int oracle_intersect(const pbr_scene_desc* sd, int n, const float* rays, float* 
                 int dirIsNeg[3] = {invDir.x < 0, invDir.y < 0, invDir.z < 0};
                 int stack[64], sp = 0, cur = 0, last = -1;
                 float lb[3] = {0, 0, 0};
-                while (true) {
+                while (!s->nodes.empty()) {   // BVHAccel::Intersect: no nodes, no hit (BVHAccel.cpp:286)
                     const OrcLinearBVHNode* nd = &s->nodes[cur];
                     Bounds3 b;
                     b.pMin = V3(nd->pMin[0], nd->pMin[1], nd->pMin[2]);
@@ -1971,7 +1971,7 @@ int oracle_intersect(const pbr_scene_desc* sd, int n, const float* rays, float* 
                         if (nd->nPrimitives > 0) {
                             for (int k = 0; k < nd->nPrimitives; ++k) {
                                 bool rec = false;
-                                float bb[3];
+                                float bb[3] = {0, 0, 0};   // a sphere hit has no barycentrics: 0 (pbr_hip.h)
                                 if (PrimIntersect(*s, nd->offset + k, ray, &si, &rec, bb)) {
                                     hit = true; last = nd->offset + k; lb[0] = bb[0]; lb[1] = bb[1]; lb[2] = bb[2];
                                 }

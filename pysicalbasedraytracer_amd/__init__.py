@@ -278,6 +278,22 @@ class HipRenderer:
                     "intersect")
         return out
 
+    def intersect_walk(self, rays, walk, any_hit=False, seg_counts=None, seg_cap=None):
+        """intersect() through one production BVH walk (capi.WALK_*): the same [n, 5] records.
+        seg_counts (capi.WALK_SEGMENTS ints) and seg_cap lay the rays out as the segmented queue of
+        the queue walks."""
+        r = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 7)
+        out = np.empty((r.shape[0], 5), dtype=np.float32)
+        sc = None
+        if seg_counts is not None:
+            sc = np.ascontiguousarray(seg_counts, dtype=np.int32)
+            if sc.shape != (capi.WALK_SEGMENTS,):
+                raise ValueError(f"seg_counts: {capi.WALK_SEGMENTS} counts")
+        self._check(self.lib.pbr_hip_intersect_walk(self.ctx, int(walk), r.shape[0], capi.fptr(r), capi.fptr(out), int(any_hit),
+                                                    int(seg_cap or 0), capi.iptr(sc) if sc is not None else None),
+                    "intersect_walk")
+        return out
+
 
 class ProgressiveRender:
     """A render that proceeds in sample passes and can stop, show, checkpoint and resume.

@@ -17,6 +17,10 @@ PBR_E_NOSCENE = -3
 PBR_E_UNSUPPORTED = -4
 PBR_E_NODEVICE = -5
 
+# enum pbr_walk (pbr_hip_intersect_walk)
+WALK_LANE, WALK_LANE_LDS, WALK_PACKET, WALK_REFILL, WALK_BINARY, WALK_REFILL_TR = range(6)
+WALK_SEGMENTS = 2048
+
 SHAPE_TRIANGLE_MESH, SHAPE_SPHERE = 0, 1
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_METAL, MAT_PLASTIC = range(6)
 LIGHT_POINT, LIGHT_DIFFUSE_AREA, LIGHT_SKYBOX, LIGHT_INFINITE_AREA = 0, 1, 2, 3
@@ -251,6 +255,8 @@ EXPORTS = {
     "pbr_hip_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(CameraDesc), C.c_int, C.POINTER(C.c_float),
                                       C.POINTER(C.c_float)]),
     "pbr_hip_intersect": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
+    "pbr_hip_intersect_walk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                         C.c_int, C.POINTER(C.c_int32)]),
     "pbr_hip_abi_version": (C.c_int, []),
     "pbr_hip_build_info": (C.c_char_p, []),
     "pbr_hip_sobol_matrices": (C.c_int, [C.c_int, C.POINTER(C.c_uint32)]),
@@ -277,7 +283,7 @@ _lib = None
 OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile", "pbr_hip_query", "pbr_hip_bounds",
                    "pbr_hip_li", "pbr_hip_set_bvh_build", "pbr_hip_bvh_build_info", "pbr_hip_build_bvh",
                    "pbr_hip_set_schedule", "pbr_hip_sample_index", "pbr_hip_sample_dimensions",
-                   "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes")
+                   "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

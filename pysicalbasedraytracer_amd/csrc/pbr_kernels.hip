@@ -795,6 +795,83 @@ __global__ void k_query(DeviceScene S, const int32_t* primIds, int n, const floa
     out[i] = o;
 }
 
+// ---- pbr_hip_intersect_walk: caller-given rays through one production walk.  The kernels below
+// are new instantiations of the walks with the template arguments and launch bounds of their
+// production users (DESIGN §3 lists them); no production kernel changes.  k_intersect's record.
+__device__ __forceinline__ void walk_record(float* o, bool any, bool hit, float t, const HitRec& h, const int32_t* primIds) {
+    o[0] = hit ? 1.f : 0.f;
+    o[1] = (hit && !any) ? t : 0.f;
+    o[2] = any ? 0.f : (hit ? (float)primIds[h.slot] : -1.f);
+    o[3] = (hit && !any) ? h.b1 : 0.f;
+    o[4] = (hit && !any) ? h.b2 : 0.f;
+}
+// traverse<ANY, false, kShortStack>: the per-lane quad walk with the LDS short stack, in
+// k_wf_shadow's workgroups and per-wave loop
+template <bool ANY>
+__global__ __launch_bounds__(256, PBR_TRAV_OCC) void k_walk_lane_lds(DeviceScene S, const int32_t* primIds, int n,
+                                                                      const float* rays, float* out) {
+    for (int i0 = blockIdx.x * blockDim.x + ((int)threadIdx.x & ~63); i0 < n; i0 += gridDim.x * blockDim.x) {   // per wave
+        const int i = i0 + (int)__lane_id();
+        if (i >= n) continue;
+        const float* rr = rays + 7 * (size_t)i;
+        Ray r = mkray(mk(rr[0], rr[1], rr[2]), mk(rr[3], rr[4], rr[5]), rr[6], -1);
+        HitRec h;
+        h.slot = -1; h.b0 = h.b1 = h.b2 = 0.f;
+        Counters c;
+        const bool hit = traverse<ANY, false, kShortStack>(S, r, &h, &c);
+        walk_record(out + 5 * (size_t)i, ANY, hit, r.tMax, h, primIds);
+    }
+}
+// traverse_wave<false>: every lane of a wave calls it, live = the lane has a ray (the camera kernels)
+__global__ __launch_bounds__(256, PBR_TRAV_OCC) void k_walk_packet(DeviceScene S, const int32_t* primIds, int n,
+                                                                    const float* rays, float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    Ray r = mkray(mk(0.f, 0.f, 0.f), mk(1.f, 1.f, 1.f), 0.f, -1);
+    if (live) {
+        const float* rr = rays + 7 * (size_t)i;
+        r = mkray(mk(rr[0], rr[1], rr[2]), mk(rr[3], rr[4], rr[5]), rr[6], -1);
+    }
+    HitRec h;
+    h.slot = -1; h.b0 = h.b1 = h.b2 = 0.f;
+    const bool hit = traverse_wave<false>(S, r, &h, live);
+    if (live) walk_record(out + 5 * (size_t)i, false, hit, r.tMax, h, primIds);
+}
+// The scratch queue of the queue walks: ray i sits at queue position pos[i] (o: origin, tMax;
+// d: direction), and its result is read back from there (hit: slot or -1, b0, b1, b2; o.w: t).
+__global__ void k_walk_scatter(int n, const int* pos, const float* rays, float4* qo, float4* qd) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* rr = rays + 7 * (size_t)i;
+    qo[pos[i]] = make_float4(rr[0], rr[1], rr[2], rr[6]);
+    qd[pos[i]] = make_float4(rr[3], rr[4], rr[5], 0.f);
+}
+__global__ void k_walk_gather(int n, const int* pos, const float4* qo, const float4* qhit, const int32_t* primIds, int any,
+                              float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 hr = qhit[pos[i]];
+    HitRec h;
+    h.slot = __float_as_int(hr.x); h.b0 = hr.y; h.b1 = hr.z; h.b2 = hr.w;
+    walk_record(out + 5 * (size_t)i, any != 0, h.slot >= 0, qo[pos[i]].w, h, primIds);
+}
+// traverse_stream<true, SHORT> over the scratch queue: SHORT = kAnyShort in k_wfp_shadow's
+// workgroups (OCC = PBR_REFILL_OCC_ANY), kShortStack in k_wfv_tr's (PBR_REFILL_OCC_TR).  A hit
+// leaves slot 0 in the queue's hit record, a miss -1.
+template <int SHORT, int OCC>
+__global__ __launch_bounds__(256, OCC) void k_walk_stream_any(DeviceScene S, const int* segCount, int segCap,
+                                                               const float4* qo, const float4* qd, float4* qhit) {
+    const int n = seg_scan(segCount);
+    traverse_stream<true, SHORT>(
+        S, n, segCap,
+        [&](int q, int* key) {
+            *key = q;
+            const float4 o = qo[q], d = qd[q];
+            return mkray(mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), o.w, -1);
+        },
+        [&](int q, bool hit, const Ray&, const HitRec&) { qhit[q] = make_float4(__int_as_float(hit ? 0 : -1), 0.f, 0.f, 0.f); });
+}
+
 // SamplerIntegrator::Li for caller-given rays (pbr_hip_li): each ray's sampler positioned at
 // (pixel, sample) with its next dimension given.
 template <int INTEGRATOR>
@@ -2736,6 +2813,116 @@ int pbr_hip_intersect(pbr_hip_ctx* ctx, int n, const float* rays, float* out, in
     HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, (size_t)n * 20, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PBR_OK;
+}
+
+int pbr_hip_intersect_walk(pbr_hip_ctx* ctx, int walk, int n, const float* rays, float* out, int any_hit, int seg_cap,
+                           const int32_t* seg_counts) {
+    static_assert(PBR_WALK_SEGMENTS == kWfBlocks, "the header's segment count is the queue kernels'");
+    if (!ctx || n < 0 || (n > 0 && (!rays || !out)) || seg_cap < 0) return PBR_E_INVALID;
+    if (walk < PBR_WALK_LANE || walk > PBR_WALK_REFILL_TR) return set_err(ctx, PBR_E_INVALID, "unknown walk");
+    if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
+    const bool any = any_hit != 0;
+    const bool queued = walk == PBR_WALK_REFILL || walk == PBR_WALK_REFILL_TR ||
+                        (walk == PBR_WALK_PACKET && (seg_cap > 0 || seg_counts));
+    if (!queued && (seg_cap > 0 || seg_counts)) return set_err(ctx, PBR_E_INVALID, "this walk reads no queue");
+    if (walk == PBR_WALK_PACKET && any) return set_err(ctx, PBR_E_UNSUPPORTED, "the packet walk has no any-hit user");
+    if (walk == PBR_WALK_REFILL_TR && !any) return set_err(ctx, PBR_E_UNSUPPORTED, "the transmittance walk is any-hit");
+    DeviceScene S = device_scene(ctx);
+    if (walk == PBR_WALK_BINARY) S.binaryWalk = 1;
+    else if (walk != PBR_WALK_LANE && S.binaryWalk)
+        return set_err(ctx, PBR_E_UNSUPPORTED, "this tree is walked in binary form: the quad walk's stack cannot hold it");
+    // the queue layout: ray i at the i-th dense position of the segments
+    std::vector<int> pos, counts;
+    if (queued) {
+        if (seg_cap == 0) {   // the fullest segment's count, or 64 entries (more when n needs them)
+            if (seg_counts) seg_cap = std::max(1, *std::max_element(seg_counts, seg_counts + kWfBlocks));
+            else seg_cap = std::max(64, (n + kWfBlocks - 1) / kWfBlocks);
+        }
+        if ((size_t)seg_cap * kWfBlocks * 48 > ((size_t)256 << 20)) return set_err(ctx, PBR_E_INVALID, "scratch queue above 256 MB");
+        counts.assign(kWfBlocks, 0);
+        long long sum = 0;
+        for (int s = 0; s < kWfBlocks; ++s) {
+            const long long c = seg_counts ? (long long)seg_counts[s] : std::min<long long>(seg_cap, (long long)n - sum);
+            if (c < 0 || c > seg_cap) return set_err(ctx, PBR_E_INVALID, "segment count outside [0, seg_cap]");
+            counts[s] = (int)c;
+            sum += c;
+        }
+        if (sum != n) return set_err(ctx, PBR_E_INVALID, "segment counts do not sum to n");
+        pos.reserve(n);
+        for (int s = 0; s < kWfBlocks; ++s)
+            for (int k = 0; k < counts[s]; ++k) pos.push_back(s * seg_cap + k);
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = drain(ctx)) return rc;
+    if (int rc = check_guard(ctx)) return rc;
+    if (n == 0) return PBR_OK;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemsetAsync(ctx->dGuard.p, 0, sizeof(int), st));
+    HIP_TRY(ctx->dScratchIn.ensure((size_t)n * 28));
+    HIP_TRY(ctx->dScratchOut.ensure((size_t)n * 20));
+    HIP_TRY(hipMemcpyAsync(ctx->dScratchIn.p, rays, (size_t)n * 28, hipMemcpyHostToDevice, st));
+    const int32_t* ids = (const int32_t*)ctx->dPrimIds.p;
+    const float* dIn = (const float*)ctx->dScratchIn.p;
+    float* dOut = (float*)ctx->dScratchOut.p;
+    const dim3 blk(256), perRay((n + 255) / 256);
+    DevBuf qO, qD, qHit, qSeg, qPos;   // the scratch queue (freed on return)
+    if (!queued) {
+        if (walk == PBR_WALK_LANE || walk == PBR_WALK_BINARY) {
+            hipLaunchKernelGGL(k_intersect, perRay, blk, 0, st, S, ids, n, dIn, dOut, any ? 1 : 0);
+        } else if (walk == PBR_WALK_LANE_LDS) {
+            const dim3 g = resident_grid(ctx, (const void*)k_wf_shadow<kShortStack>);
+            if (any) hipLaunchKernelGGL(k_walk_lane_lds<true>, g, blk, 0, st, S, ids, n, dIn, dOut);
+            else hipLaunchKernelGGL(k_walk_lane_lds<false>, g, blk, 0, st, S, ids, n, dIn, dOut);
+        } else {
+            hipLaunchKernelGGL(k_walk_packet, perRay, blk, 0, st, S, ids, n, dIn, dOut);
+        }
+        HIP_TRY(hipGetLastError());
+    } else {
+        const size_t entries = (size_t)seg_cap * kWfBlocks;
+        HIP_TRY(qO.ensure(entries * 16));
+        HIP_TRY(qD.ensure(entries * 16));
+        HIP_TRY(qHit.ensure(entries * 16));
+        HIP_TRY(hipMemsetAsync(qO.p, 0, entries * 16, st));
+        HIP_TRY(hipMemsetAsync(qD.p, 0, entries * 16, st));
+        HIP_TRY(hipMemsetAsync(qHit.p, 0, entries * 16, st));
+        HIP_TRY(qSeg.upload(counts, st));
+        HIP_TRY(qPos.upload(pos, st));
+        hipLaunchKernelGGL(k_walk_scatter, perRay, blk, 0, st, n, (const int*)qPos.p, dIn, (float4*)qO.p, (float4*)qD.p);
+        HIP_TRY(hipGetLastError());
+        if (!any) {   // the production kernels themselves: the queue is their whole input and output
+            WfParams W;
+            std::memset(&W, 0, sizeof(W));
+            W.P.S = S;
+            W.segCap = seg_cap;
+            W.cur.o = (float4*)qO.p;
+            W.cur.d = (float4*)qD.p;
+            W.cur.hit = (float4*)qHit.p;
+            W.cur.segCount = (int*)qSeg.p;
+            if (walk == PBR_WALK_REFILL)
+                hipLaunchKernelGGL((k_wf_extend<kShortStack, true>), resident_grid(ctx, (const void*)k_wf_extend<kShortStack, true>),
+                                   blk, 0, st, W);
+            else
+                hipLaunchKernelGGL(k_wf_extend<kShortStack>, resident_grid(ctx, (const void*)k_wf_extend<kShortStack>), blk, 0, st, W);
+        } else if (walk == PBR_WALK_REFILL) {
+            hipLaunchKernelGGL((k_walk_stream_any<kAnyShort, PBR_REFILL_OCC_ANY>),
+                               resident_grid(ctx, (const void*)k_wfp_shadow<kShortStack>), blk, 0, st, S, (const int*)qSeg.p,
+                               seg_cap, (const float4*)qO.p, (const float4*)qD.p, (float4*)qHit.p);
+        } else {
+            hipLaunchKernelGGL((k_walk_stream_any<kShortStack, PBR_REFILL_OCC_TR>),
+                               resident_grid(ctx, (const void*)k_wfv_tr<kShortStack>), blk, 0, st, S, (const int*)qSeg.p, seg_cap,
+                               (const float4*)qO.p, (const float4*)qD.p, (float4*)qHit.p);
+        }
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_walk_gather, perRay, blk, 0, st, n, (const int*)qPos.p, (const float4*)qO.p, (const float4*)qHit.p,
+                           ids, any ? 1 : 0, dOut);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(out, dOut, (size_t)n * 20, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctx->guardHost, ctx->dGuard.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(ctx->evGuard, st));
+    ctx->guardPending = true;
+    HIP_TRY(hipStreamSynchronize(st));   // (the scratch queue is freed after this)
+    return check_guard(ctx);
 }
 
 }  // extern "C"

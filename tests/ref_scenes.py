@@ -344,6 +344,271 @@ def intersect_case():
     return s, rays
 
 
+def grid_mesh(n=6, z=0.0):
+    """n×n unit squares in the z plane, two triangles each, vertices on integer coordinates."""
+    xs = np.arange(n + 1, dtype=np.float32)
+    P = np.array([(x, y, z) for y in xs for x in xs], np.float32)
+    I = []
+    for j in range(n):
+        for i in range(n):
+            a, b, c, d = j * (n + 1) + i, j * (n + 1) + i + 1, (j + 1) * (n + 1) + i, (j + 1) * (n + 1) + i + 1
+            I += [(a, b, d), (a, d, c)]
+    return P, np.array(I, np.int32)
+
+
+# ---------------------------------------------------------------- rays for the production BVH walks
+# (tests/test_gpu_walks.py, tests/golden/make_walk_fixtures.py).  Everything is seeded; no ray
+# component other than tMax = +inf is non-finite and no direction is all zero.
+WALK_N = 4   # the lattice spans [0, WALK_N]^3
+
+
+def lattice_scene(n=WALK_N):
+    """Sheets of grid_mesh(n) at z = 0..n and the same sheets permuted to the x and y planes:
+    3 (n + 1) meshes whose every BVH box face lies on an integer plane."""
+    s = scenes.Scene()
+    m = s.matte((0.5, 0.5, 0.5))
+    P, I = grid_mesh(n)
+    for k in range(n + 1):
+        Q = P + np.float32([0, 0, k])
+        s.mesh(Q, I, m)
+        s.mesh(Q[:, [2, 0, 1]].copy(), I, m)
+        s.mesh(Q[:, [1, 2, 0]].copy(), I, m)
+    return s
+
+
+def rays_axis(n=WALK_N):
+    """Direction ±1 on one axis, the other two components each of +0 and -0 (invDir = ±inf, and
+    0·inf = NaN where the origin lies on a box plane); origins on the half-integer grid one unit
+    outside [0, n]^3."""
+    R = []
+    coords = np.arange(0, n + 0.01, 0.5)
+    for ax in range(3):
+        for sgn in (1.0, -1.0):
+            for z1 in (0.0, -0.0):
+                for z2 in (0.0, -0.0):
+                    for a in coords:
+                        for b in coords:
+                            o, d = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
+                            o[ax] = -1.0 if sgn > 0 else n + 1.0
+                            o[(ax + 1) % 3], o[(ax + 2) % 3] = a, b
+                            d[ax], d[(ax + 1) % 3], d[(ax + 2) % 3] = sgn, z1, z2
+                            R.append(o + d + [np.inf])
+    return np.array(R, np.float32)
+
+
+def rays_plane(n=WALK_N, seed=1, per=40):
+    """One direction component ±0 with the origin on an integer plane of that axis (the ray slides
+    along box faces); the other components random."""
+    rng = np.random.default_rng(seed)
+    R = []
+    for ax in range(3):
+        for k in range(n + 1):
+            for _ in range(per):
+                o = rng.uniform(-1, n + 1, 3)
+                o[ax] = k
+                d = rng.normal(size=3)
+                d[ax] = rng.choice([0.0, -0.0])
+                R.append(list(o) + list(d) + [np.inf])
+    return np.array(R, np.float32)
+
+
+def rays_octants(n=WALK_N, seed=2, count=512, lo=0.1, hi=None):
+    """All eight direction-sign classes interleaved ray by ray (every wave of 64 holds all eight);
+    origins uniform in [lo, hi]^3 (default: inside the lattice, so every ray hits)."""
+    import itertools
+    hi = n - 0.1 if hi is None else hi
+    rng = np.random.default_rng(seed)
+    signs = list(itertools.product((1, -1), repeat=3))
+    R = []
+    for i in range(count):
+        sg = np.array(signs[i % 8], np.float64)
+        o = rng.uniform(lo, hi, 3)
+        d = np.abs(rng.normal(size=3)) * sg
+        R.append(list(o) + list(d) + [np.inf])
+    return np.array(R, np.float32)
+
+
+def rays_toward(P, I, seed, count):
+    """Rays for a small mesh (P, I): a third towards random interior points of random triangles, a
+    third exactly at their vertices and edge midpoints from an axis-aligned offset (two direction
+    components ±0, edge functions exactly zero), a third towards random points around the mesh."""
+    rng = np.random.default_rng(seed)
+    lo, hi = P.min(0) - 1.0, P.max(0) + 1.0
+    k = count // 3
+    tri = I[rng.integers(0, len(I), 2 * k)]
+    w = rng.dirichlet((1.0, 1.0, 1.0), k)
+    tgt_in = (w[:, :, None] * P[tri[:k]]).sum(1)
+    e = rng.integers(0, 3, k)
+    a = P[tri[k:][np.arange(k), e]]
+    b = P[tri[k:][np.arange(k), (e + 1) % 3]]
+    mid = rng.integers(0, 2, k)[:, None]
+    tgt_ve = np.where(mid == 1, (a + b) * 0.5, a)
+    org_in = rng.uniform(lo - 1.0, hi + 1.0, (k, 3))
+    ax = rng.integers(0, 3, k)
+    off = np.zeros((k, 3))
+    off[np.arange(k), ax] = rng.choice([-2.0, 1.5, 3.0], k)
+    org_ve = tgt_ve + off
+    d_ve = -off * rng.choice([1.0, 0.5], k)[:, None]
+    d_ve[d_ve == 0] = rng.choice([0.0, -0.0], int((d_ve == 0).sum()))
+    m = count - 2 * k
+    org_r = rng.uniform(lo - 1.0, hi + 1.0, (m, 3))
+    d_r = rng.uniform(lo, hi, (m, 3)) - org_r
+    o = np.concatenate([org_in, org_ve, org_r])
+    d = np.concatenate([tgt_in - org_in, d_ve, d_r])
+    tmax = np.full((count, 1), np.inf)
+    tmax[::11] = 1.0   # some rays end at or before their target
+    return np.concatenate([o, d, tmax], 1).astype(np.float32)
+
+
+def with_tmax_ties(scene, rays):
+    """Every ray of `rays` the oracle's closest hit reaches, three more times: tMax = the hit
+    distance t, nextafter(t, +inf) and nextafter(t, 0)."""
+    import oracle_lib as O
+    c = O.intersect(scene, rays, False)
+    h = c[:, 0] > 0
+    t = c[h, 1].astype(np.float32)
+    out = []
+    for tm in (t, np.nextafter(t, np.float32(np.inf)), np.nextafter(t, np.float32(0))):
+        r = rays[h].copy()
+        r[:, 6] = tm
+        out.append(r)
+    return np.concatenate(out)
+
+
+_walk_case = None
+
+
+def walk_case():
+    """(lattice scene, {class name: rays [k, 7]}) — the ray classes no camera or BSDF produces:
+    axis, plane, octants_in (all hit), octants_out (origins in [-1, n + 1]^3: some miss), tmax_ties
+    (every hit ray of the four, at tMax = t and one ulp either side)."""
+    global _walk_case
+    if _walk_case is None:
+        s = lattice_scene()
+        cls = {"axis": rays_axis(), "plane": rays_plane(), "octants_in": rays_octants(),
+               "octants_out": rays_octants(seed=3, lo=-1.0, hi=WALK_N + 1.0)}
+        cls["tmax_ties"] = with_tmax_ties(s, np.concatenate(list(cls.values())))
+        _walk_case = (s, cls)
+    return _walk_case
+
+
+def walk_fixture_rays():
+    """(scene, rays, [[class, count]]) — the classes of walk_case() concatenated in name order: the
+    rays of tests/golden/walk_rays.json (make_walk_fixtures.py)."""
+    s, cls = walk_case()
+    names = sorted(cls)
+    return s, np.concatenate([cls[k] for k in names]), [[k, int(len(cls[k]))] for k in names]
+
+
+def load_walk_fixture():
+    """tests/golden/walk_rays.json → (closest records [n, 3] float32 {hit, t, prim} as the
+    `intersect` fixture holds them, any-hit flags uint8 [n], the fixture's dict)."""
+    import base64
+    import json
+    import os
+    f = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "walk_rays.json")))
+    n = f["n"]
+
+    def dec(k, dt):
+        return np.frombuffer(base64.b64decode(f[k]), dtype=dt)
+
+    h = np.unpackbits(dec("hit", np.uint8))[:n].astype(bool)
+    ref = np.zeros((n, 3), np.float32)
+    ref[:, 0] = h
+    ref[h, 1] = dec("t", "<f4")
+    ref[:, 2] = -1
+    ref[h, 2] = dec("prim", "<i2")
+    return ref, np.unpackbits(dec("any", np.uint8))[:n], f
+
+
+def walk_mixed(count=None, seed=7):
+    """The lattice classes concatenated in a seeded random order (every prefix mixes the classes)."""
+    _, cls = walk_case()
+    r = np.concatenate([cls[k] for k in sorted(cls)])
+    r = r[np.random.default_rng(seed).permutation(len(r))]
+    return r if count is None else r[:count]
+
+
+def walk_wave_shapes():
+    """{name: rays} on the lattice scene: n = 1, 63, 64, 65 and 129 rays, and waves whose only live
+    lane is lane 0, 31 or 63 — the other lanes hold axis rays with tMax = 0, which start outside the
+    root box and so fail the root test (dead lanes of a packet); two waves each."""
+    _, cls = walk_case()
+    mixed = walk_mixed()
+    out = {f"n{n}": mixed[:n].copy() for n in (1, 63, 64, 65, 129)}
+    dead = cls["axis"][::13][:128].copy()
+    dead[:, 6] = 0.0
+    live = cls["octants_in"]
+    for lane in (0, 31, 63):
+        r = dead.copy()
+        r[lane] = live[lane]
+        r[64 + lane] = live[64 + lane]
+        out[f"lone_lane{lane}"] = r
+    return out
+
+
+def walk_small_scenes():
+    """{name: (scene, rays)} — trees at the small end: triangle subsets of grid_mesh(2) (the
+    oracle's trees: empty, 1, 1, 3, 5 and 7 nodes), multi-primitive leaves, spheres next to a mesh."""
+    out = {}
+    P, I = grid_mesh(2)
+    for nt in (0, 1, 2, 3, 5, 8):
+        s = scenes.Scene()
+        if nt:
+            s.mesh(P, I[:nt], s.matte((0.5, 0.5, 0.5)))
+        out[f"tris{nt}"] = (s, rays_toward(P, I[:max(nt, 1)], seed=20 + nt, count=600))
+    s = scenes.Scene()
+    s.mesh(P, I, s.matte((0.5, 0.5, 0.5)))
+    s.max_prims_in_node = 4
+    out["tris8_max4"] = (s, rays_toward(P, I, seed=31, count=600))
+    s = scenes.Scene()
+    m = s.matte((0.5, 0.5, 0.5))
+    P4, I4 = grid_mesh(4)
+    s.mesh(P4, I4, m)
+    s.sphere((1.0, 1.0, 1.0), 0.75, m)
+    s.sphere((3.0, 2.5, -1.0), 0.5, m)
+    sph = np.array([(1.0, 1.0, 1.0), (1.75, 1.0, 1.0), (3.0, 2.5, -1.0), (3.0, 2.5, -0.5), (1.0, 0.25, 1.0)], np.float32)
+    Ps = np.concatenate([P4, sph])
+    Is = np.concatenate([I4, np.array([(25, 26, 29), (27, 28, 25)], np.int32)])   # targets on the spheres too
+    out["mesh_two_spheres"] = (s, rays_toward(Ps, Is, seed=32, count=900))
+    return out
+
+
+def walk_seg_layouts(seed=11):
+    """[(name, n, seg_cap, counts or None)] — segment layouts of a queue of capi.WALK_SEGMENTS
+    segments for the first n rays of a set: the edge cases of the queue kernels' dense-index →
+    position lookup (a 64-way ballot over coarse buckets of 32 segments, then a 32-way one)."""
+    S = capi.WALK_SEGMENTS
+    rng = np.random.default_rng(seed)
+    out = [("dense_cap64", 2000, 64, None), ("dense_cap3", 2000, 3, None), ("dense_n1", 1, 1, None)]
+    for seg in (0, 1000, S - 1):
+        c = np.zeros(S, np.int32)
+        c[seg] = 300
+        out.append((f"all_in_seg{seg}", 300, 300, c))
+    c = np.zeros(S, np.int32)
+    c[::37] = 1
+    out.append(("every_37th", int(c.sum()), 2, c))
+    c = np.zeros(S, np.int32)   # the last and first segment of each coarse bucket
+    edge = np.array(sorted(set(range(0, S, 32)) | set(range(31, S, 32))))
+    c[edge] = 1 + np.arange(len(edge)) % 5
+    out.append(("bucket_edges", int(c.sum()), 5, c))
+    # a wave looks up 64 consecutive dense indices [64 w, 64 w + 63]: coarse buckets whose first
+    # offset is exactly a wave's first index, and exactly its last
+    c = np.zeros(S, np.int32)
+    c[0:32 * 32:32] = 64
+    out.append(("bucket_offset_is_wave_first", int(c.sum()), 64, c))
+    c = c.copy()
+    c[0] = 63
+    out.append(("bucket_offset_is_wave_last", int(c.sum()), 64, c))
+    c = rng.integers(1, 7, S).astype(np.int32)
+    c[rng.random(S) < 0.6] = 0
+    out.append(("random_60pct_empty", int(c.sum()), 6, c))
+    c = np.zeros(S, np.int32)
+    c[1234] = 1
+    out.append(("one_ray_seg1234", 1, 1, c))
+    return out
+
+
 def camera_case():
     rng = np.random.default_rng(5)
     cams = [scenes.camera(48, 27, **CAM_C), scenes.camera(27, 48, (1.0, 2.0, -3.0), (0.2, 0.1, 0.0))]
