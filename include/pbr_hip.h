@@ -365,7 +365,10 @@ typedef struct pbr_schedule {
     int chunk_log2;             /* at most 2^chunk_log2 samples per chunk (10..28; 0 = the default: 25 for
                                  * Whitted, less with several lights; for Path / VolPath the largest of
                                  * 2^20..2^27 whose lanes' queues fit 3/4 of the device memory free or held
-                                 * by the context); capped at 25 (Whitted) and 27 (Path / VolPath) */
+                                 * by the context — 2^26 on 3 lanes when that memory cannot be queried; Whitted's
+                                 * default shrinks in the same way on a device with less room than its lanes
+                                 * need); capped at 25 (Whitted) and 27 (Path / VolPath).  24 or more chunks are
+                                 * made equal, a whole number per lane: see pbr_hip_plan_chunks */
     int lanes;                  /* chunk lanes, each its own stream and queues (1..4); 0 = 3 (Path: 4 where
                                  * four lanes of 2^27-sample chunks fit the memory share above) */
     int fuse_camera;            /* pbr_fuse_mode */
@@ -373,6 +376,51 @@ typedef struct pbr_schedule {
                                  * (one lane, no shadow stream) — measures each kernel on its own */
 } pbr_schedule;
 int pbr_hip_set_schedule(pbr_hip_ctx* ctx, const pbr_schedule* sched);
+
+/* ---- the chunk plan (no reference counterpart) ----
+ * How the wavefront schedules cut a frame into chunks over lanes: a pure function of the schedule
+ * request, the frame and the memory the lanes may take.  The renders take every chunking decision
+ * from it, so a test (or a caller sizing its own buffers) can ask for the plan instead of restating
+ * the rule. */
+typedef struct pbr_chunk_query {
+    int integrator;             /* pbr_integrator_type */
+    int64_t n_pixels;           /* pixels of the frame (the sum of its tiles) */
+    int spp;                    /* samples per pixel of one frame (render_passes: of one pass) */
+    int max_depth;
+    int n_lights;               /* lights of the scene */
+    int sky_light;              /* 1: the scene's single light is a SkyBox */
+    int batch;                  /* 1: pbr_hip_render_frames / pbr_hip_render_passes, 0: pbr_hip_render */
+    int scene_fusable;          /* 1: the scene's materials allow Whitted's fused level-0 shade (untextured
+                                 * matte / mirror / simple lobes, few enough to stage in LDS) */
+    double lane_budget;         /* bytes the lanes' buffers may take: 3/4 of the device memory free or held
+                                 * by the context's lanes; 0 = unknown (the memory query failed): Whitted
+                                 * keeps its default chunk, Path / VolPath plan 2^26-sample chunks on 3 lanes */
+} pbr_chunk_query;
+typedef struct pbr_chunk_plan {
+    int lanes;                  /* 1..4; 0 (with n_chunks 0): the call ran the megakernel, which has no chunks */
+    int chunk_log2;             /* the chosen bound: at most 2^chunk_log2 samples per chunk */
+    int64_t chunk_pixels;       /* chunk c covers packed pixels [c·chunk_pixels, min((c+1)·chunk_pixels, n_pixels)) */
+    int64_t n_chunks;
+    uint64_t cap;               /* samples of a whole chunk: chunk_pixels · spp */
+    uint64_t qcap;              /* entries of a lane's queues: >= cap and >= seg_cap · PBR_WALK_SEGMENTS */
+    int seg_cap;                /* entries of one queue segment (a multiple of 256) */
+    int lane0_on_ctx_stream;    /* pbr_hip_last_chunks: 1 when lane 0 ran on the context's stream and not on the
+                                 * caller's (four lanes and a caller's stream) */
+    int fused_camera;           /* Whitted: the level-0 shade traced its own camera rays */
+    int reserved;
+    double bytes_per_sample;    /* estimate of one lane's buffers per queue entry; an upper bound:
+                                 * lanes · bytes_per_sample · qcap >= what the lanes allocate */
+    double lane_budget;         /* the budget the plan was made for */
+    uint64_t held_lane_bytes;   /* pbr_hip_last_chunks: bytes the context's lane buffers hold (they grow to the
+                                 * largest plan rendered and are never shrunk) */
+} pbr_chunk_plan;
+/* The plan for `query` under `sched` (NULL = the defaults).  No context, no GPU call.  PBR_E_INVALID:
+ * a NULL query or out, an unknown integrator, n_pixels or spp < 1, a schedule pbr_hip_set_schedule
+ * would reject. */
+int pbr_hip_plan_chunks(const pbr_schedule* sched, const pbr_chunk_query* query, pbr_chunk_plan* out);
+/* The plan the context's last pbr_hip_render, pbr_hip_render_frames or pbr_hip_render_passes call ran,
+ * with the budget computed for that call and the bytes the lane buffers hold after it. */
+int pbr_hip_last_chunks(pbr_hip_ctx* ctx, pbr_chunk_plan* out);
 
 /* ---- per-kernel profile (measurement; no reference counterpart) ----
  * While profiling is on, every kernel launch of a render is bracketed by a HIP event pair on the

@@ -167,6 +167,20 @@ class HipRenderer:
         s = capi.Schedule(kernels, chunk_log2, lanes, fuse_camera, int(serial))
         self._check(self.lib.pbr_hip_set_schedule(self.ctx, C.byref(s)), "set_schedule")
 
+    def last_chunks(self) -> dict:
+        """The chunk plan the last render, render_frames or render_passes call ran (pbr_hip_last_chunks):
+        lanes, chunk_pixels, n_chunks, queue capacities, the budget computed for that call, the bytes
+        the lane buffers hold, whether lane 0 ran on the context's stream and whether the camera was
+        fused.  lanes == 0 and n_chunks == 0: the call ran the megakernel."""
+        out = capi.ChunkPlan()
+        self._check(self.lib.pbr_hip_last_chunks(self.ctx, C.byref(out)), "last_chunks")
+        return out.as_dict()
+
+    @staticmethod
+    def plan_chunks(integrator, n_pixels, spp, max_depth, **kw) -> dict:
+        """The plan for such a frame without rendering it (capi.plan_chunks; no GPU call)."""
+        return capi.plan_chunks(integrator, n_pixels, spp, max_depth, **kw)
+
     def set_profiling(self, on: bool = True):
         """Start (on) or stop a per-kernel measurement window (pbr_hip_set_profiling)."""
         self._check(self.lib.pbr_hip_set_profiling(self.ctx, int(on)), "set_profiling")

@@ -230,6 +230,39 @@ class Schedule(C.Structure):
                 ("serial", C.c_int)]
 
 
+class ChunkQuery(C.Structure):
+    _fields_ = [("integrator", C.c_int), ("n_pixels", C.c_int64), ("spp", C.c_int), ("max_depth", C.c_int),
+                ("n_lights", C.c_int), ("sky_light", C.c_int), ("batch", C.c_int), ("scene_fusable", C.c_int),
+                ("lane_budget", C.c_double)]
+
+
+class ChunkPlan(C.Structure):
+    _fields_ = [("lanes", C.c_int), ("chunk_log2", C.c_int), ("chunk_pixels", C.c_int64), ("n_chunks", C.c_int64),
+                ("cap", C.c_uint64), ("qcap", C.c_uint64), ("seg_cap", C.c_int), ("lane0_on_ctx_stream", C.c_int),
+                ("fused_camera", C.c_int), ("reserved", C.c_int), ("bytes_per_sample", C.c_double),
+                ("lane_budget", C.c_double), ("held_lane_bytes", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        d = {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+        d["lane0_on_ctx_stream"] = bool(d["lane0_on_ctx_stream"])
+        d["fused_camera"] = bool(d["fused_camera"])
+        return d
+
+
+def plan_chunks(integrator, n_pixels, spp, max_depth, n_lights=1, sky_light=False, batch=False, lane_budget=0.0,
+                scene_fusable=True, schedule: "Schedule | None" = None, lib=None) -> dict:
+    """pbr_hip_plan_chunks: how the wavefront schedules would cut such a frame into chunks over lanes
+    (no context, no GPU call).  lane_budget in bytes, 0 = unknown; schedule None = the defaults."""
+    q = ChunkQuery(int(integrator), int(n_pixels), int(spp), int(max_depth), int(n_lights), int(bool(sky_light)),
+                   int(bool(batch)), int(bool(scene_fusable)), float(lane_budget))
+    out = ChunkPlan()
+    rc = (lib or load_library()).pbr_hip_plan_chunks(C.byref(schedule) if schedule is not None else None, C.byref(q),
+                                                     C.byref(out))
+    if rc != PBR_OK:
+        raise ValueError(f"plan_chunks: invalid query or schedule ({rc})")
+    return out.as_dict()
+
+
 # Every symbol include/pbr_hip.h declares, with its ctypes signature.
 EXPORTS = {
     "pbr_hip_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -265,6 +298,8 @@ EXPORTS = {
     "pbr_hip_li": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int32),
                              C.c_int, C.POINTER(C.c_float)]),
     "pbr_hip_set_schedule": (C.c_int, [C.c_void_p, C.POINTER(Schedule)]),
+    "pbr_hip_plan_chunks": (C.c_int, [C.POINTER(Schedule), C.POINTER(ChunkQuery), C.POINTER(ChunkPlan)]),
+    "pbr_hip_last_chunks": (C.c_int, [C.c_void_p, C.POINTER(ChunkPlan)]),
     "pbr_hip_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),
     "pbr_hip_get_profile": (C.c_int, [C.c_void_p, C.POINTER(KernelProfile), C.c_int, C.POINTER(C.c_int)]),
     "pbr_hip_set_bvh_build": (C.c_int, [C.c_void_p, C.c_int]),
@@ -283,7 +318,8 @@ _lib = None
 OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile", "pbr_hip_query", "pbr_hip_bounds",
                    "pbr_hip_li", "pbr_hip_set_bvh_build", "pbr_hip_bvh_build_info", "pbr_hip_build_bvh",
                    "pbr_hip_set_schedule", "pbr_hip_sample_index", "pbr_hip_sample_dimensions",
-                   "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk")
+                   "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk",
+                   "pbr_hip_plan_chunks", "pbr_hip_last_chunks")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

@@ -23,6 +23,7 @@
 #include "../../include/pbr_hip.h"
 #include "pbr_device.h"
 #include "pbr_scene.h"
+#include "pbr_chunk_plan.h"
 
 using namespace pbr;
 
@@ -942,18 +943,20 @@ struct WfBufs {
     DevBuf wPassList, wPassCnt;       // the classed Path shade: passes 1..'s queue positions, counts
     DevBuf wpO, wpD, wpId, sL, rA, rB, rBeta, rLi, rFlags, rLight, rTgt;
     DevBuf wtO, wtD, wtP, wtE, wtN, wtId, rLiA, rTr, rWA;   // VolPath transmittance walk
+    // device bytes this lane holds: every member above (lane_budget, pbr_hip_last_chunks)
+    size_t bytes() const {
+        size_t n = 0;
+        for (int k = 0; k < 2; ++k) n += wqO[k].bytes + wqD[k].bytes + wqId[k].bytes + wqHit[k].bytes + wqS0[k].bytes + wqS1[k].bytes;
+        n += wsO.bytes + wsD.bytes + wsC.bytes + wsId.bytes + wRecA.bytes + wRecF.bytes + wRecP.bytes + wDepth.bytes + wIndex.bytes + wCnt.bytes;
+        n += wsO2.bytes + wsD2.bytes + wsC2.bytes + wsId2.bytes + wsW.bytes + wsW2.bytes + wRecC.bytes + wRecV.bytes;
+        n += wPassList.bytes + wPassCnt.bytes;
+        n += wpO.bytes + wpD.bytes + wpId.bytes + sL.bytes + rA.bytes + rB.bytes + rBeta.bytes + rLi.bytes + rFlags.bytes + rLight.bytes + rTgt.bytes;
+        n += wtO.bytes + wtD.bytes + wtP.bytes + wtE.bytes + wtN.bytes + wtId.bytes + rLiA.bytes + rTr.bytes + rWA.bytes;
+        return n;
+    }
 };
-// Chunks alternate between two lanes (own buffers, own stream) so one chunk's launch tails overlap
-// the other's work — what keeps a small per-GPU shard of a multi-GPU frame efficient.
-// Lanes a frame may use (pbr_schedule::lanes), and the default.  Measured (frame ms, bit-identical):
-// C2 2 lanes 17.73-17.80, 3: 17.49, 4: 17.97 (4 lanes of 2^24-sample chunks 19.10); C3 268.7 /
-// 267.3 / 274.9; C5 1396 / 1379 / 1414.
-constexpr int kWfLanes = 4;
-#ifndef PBR_LANES_DEFAULT
-#define PBR_LANES_DEFAULT 3
-#endif
-constexpr int kWfDefaultLanes = PBR_LANES_DEFAULT;
-
+// (a member added to WfBufs must be added to bytes(): 52 buffers)
+static_assert(sizeof(WfBufs) == 52 * sizeof(DevBuf), "WfBufs::bytes() sums every member");
 struct pbr_hip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -985,7 +988,9 @@ struct pbr_hip_ctx {
     // wavefront buffers of the two chunk lanes, and the lane-1 stream with its fork/join events
     WfBufs wb[kWfLanes];
     hipStream_t side[kWfLanes] = {};     // lanes 1.. (lane 0: the caller's stream, or ctx->stream — wf_fork)
-    hipStream_t lane0 = nullptr;         // lane 0's stream in the current frame or batch (wf_fork)
+    hipStream_t lane0 = nullptr;         // lane 0's stream in the current frame or batch (render_impl, wf_fork)
+    WfChunks lastPlan = wf_no_chunks();  // what the last render call ran (pbr_hip_last_chunks); lanes 0: the megakernel
+    bool lastOwnLane0 = false;           // ... with lane 0 on the context's stream
     hipEvent_t evFork = nullptr, evJoin[kWfLanes] = {};
     struct FrameEv {                     // a batch: the end of frame f's last chunk on each lane it used
         hipEvent_t ev[kWfLanes] = {};
@@ -1248,74 +1253,6 @@ int upload_light_distribution(pbr_hip_ctx* ctx, int strategy) {
 }
 
 
-// Chunking of the wavefront schedules: at most 2^chunkLog2 samples per chunk; chunks alternate
-// over the lanes.  Measured on C2: two lanes 23.4 ms vs 24.9 for one; forcing a one-chunk
-// (1/8-frame shard) frame into two concurrent half chunks was slower (4.00 vs 3.86 ms).
-struct WfChunks {
-    long long chunkPix = 1;
-    int lanes = 1;
-    size_t cap = 0;   // samples of the largest chunk
-    int segCap = 0;   // capacity of one queue segment
-    size_t qcap = 0;  // queue entries
-};
-// A batch's one-chunk frames rotate over the lanes, and every lane holds queue and record buffers for
-// the whole frame: they keep several lanes only while the lanes' buffers together stay within this
-// many bytes (bytesPerSample × samples per lane, estimated from the schedule's buffers).  A C2 rank
-// shard (≤ 2^25 samples, ≈ 12 GB per lane) keeps three; a Path frame at the 2^26-sample cap (≈ 23
-// GB per lane) two; the single-frame call would run such a frame on one lane.
-constexpr double kBatchLaneBytes = 48e9;
-// The largest chunk a Whitted schedule accepts (its default is 2^25, less with several lights).
-// Measured, C2 in 5-frame batches (bit-identical): 2^25 (four chunks) 13.62-13.69 ms, 2^26 14.39-14.61,
-// 2^27 14.16-14.25 (profiles/r6_c2_chunk_ab.log).
-#ifndef PBR_WF_WHITTED_MAXLOG2
-#define PBR_WF_WHITTED_MAXLOG2 25
-#endif
-// laneBudget > 0 (the Path / VolPath schedules, lane_budget): the default chunk is the largest
-// 2^k <= 2^maxLog2 samples whose lanes' buffers fit that many bytes (not below 2^minLog2), and a
-// batch's one-chunk frames keep as many lanes as fit it; 0: the default is 2^maxLog2 and the batch
-// budget kBatchLaneBytes.  A requested chunk_log2 is capped at maxLog2 either way.
-// wideLanes > the default lane count: the default lanes when that many lanes of 2^maxLog2-sample
-// chunks fit laneBudget (the Path schedule: 4).
-WfChunks wf_chunks(const pbr_schedule& sch, const KParams& P, int maxLog2 = 25, bool batch = false,
-                   double bytesPerSample = 0, double laneBudget = 0, int defLog2 = 0, int minLog2 = 20,
-                   int wideLanes = 0) {
-    WfChunks c;
-    c.lanes = sch.serial ? 1 : (sch.lanes > 0 ? sch.lanes : kWfDefaultLanes);
-    if (!sch.serial && sch.lanes == 0 && wideLanes > c.lanes && sch.chunk_log2 == 0 && defLog2 == 0 &&
-        wideLanes * bytesPerSample * (double)(1LL << maxLog2) <= laneBudget)
-        c.lanes = std::min(wideLanes, kWfLanes);
-    int chunkLog2 = maxLog2;
-    if (sch.chunk_log2 > 0) chunkLog2 = std::min(sch.chunk_log2, maxLog2);
-    else if (defLog2 > 0) chunkLog2 = std::min(defLog2, maxLog2);
-    else if (laneBudget > 0 && bytesPerSample > 0)
-        while (chunkLog2 > minLog2 && c.lanes * bytesPerSample * (double)(1LL << chunkLog2) > laneBudget) --chunkLog2;
-    c.chunkPix = std::max(1LL, (1LL << chunkLog2) / P.spp);
-    if (c.chunkPix >= P.nPixels) {   // one chunk: splitting a small frame only adds launch tails
-        c.chunkPix = P.nPixels;
-        if (!batch) c.lanes = 1;     // (a batch's one-chunk frames rotate over the lanes)
-        else if (c.lanes > 1 && bytesPerSample > 0) {
-            const double perLane = bytesPerSample * (double)P.nPixels * (double)P.spp;
-            const double budget = laneBudget > 0 ? laneBudget : kBatchLaneBytes;
-            c.lanes = (int)std::max(1.0, std::min((double)c.lanes, std::floor(budget / perLane)));
-        }
-    } else {
-        // Many chunks: make them equal and a whole number per lane (the count rounded down to a
-        // multiple of the lanes), so no lane runs a last chunk alone.  Measured (bit-identical,
-        // frame ms; default / rounded down / rounded up): C5 (32 chunks) 1215 / 1193 / 1200, C4
-        // (254) 6628 / 6587 / 6572, C3 (16) 257.0 / 257.5 / 268.3, C2 (4) 17.5 / 18.6 / 18.3 —
-        // with few chunks the power-of-two size wins, so only 24 or more are balanced.
-        long long n = (P.nPixels + c.chunkPix - 1) / c.chunkPix;
-        if (n >= 24) {
-            n = std::max<long long>(c.lanes, n / c.lanes * c.lanes);
-            c.chunkPix = (P.nPixels + n - 1) / n;
-        }
-    }
-    c.cap = (size_t)c.chunkPix * P.spp;
-    // a shade workgroup processes at most ceil(cap / (kWfBlocks·256)) rounds of 256
-    c.segCap = (int)((c.cap + (size_t)kWfBlocks * 256 - 1) / ((size_t)kWfBlocks * 256) * 256);
-    c.qcap = std::max(c.cap, (size_t)c.segCap * kWfBlocks);
-    return c;
-}
 // Bytes the Path / VolPath lane buffers may take: a share of the device memory that is free or
 // already held by this context's lanes (their buffers are reused and grown, never shrunk).  On an
 // MI355X (288 GB) that is room for three lanes of 2^27-sample chunks; another large allocation on the
@@ -1323,16 +1260,15 @@ WfChunks wf_chunks(const pbr_schedule& sch, const KParams& P, int maxLog2 = 25, 
 // single frames, three lanes): C4 2^26 4379 → 2^27 4189, C5 815.6 → 771.4, C3 205.0 → 203.6; 2^24
 // and 2^23 were 25-50% slower (profiles/r6_sched_sweep*.log).
 constexpr double kLaneMemShare = 0.75;
+size_t held_lane_bytes(const pbr_hip_ctx* ctx) {
+    size_t held = 0;
+    for (int l = 0; l < kWfLanes; ++l) held += ctx->wb[l].bytes();
+    return held;
+}
 double lane_budget(pbr_hip_ctx* ctx) {
     size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return 0;   // the fixed defaults
-    static_assert(sizeof(WfBufs) % sizeof(DevBuf) == 0, "WfBufs holds DevBuf members only");
-    double held = 0;
-    for (int l = 0; l < kWfLanes; ++l) {
-        const DevBuf* b = reinterpret_cast<const DevBuf*>(&ctx->wb[l]);
-        for (size_t i = 0; i < sizeof(WfBufs) / sizeof(DevBuf); ++i) held += (double)b[i].bytes;
-    }
-    return kLaneMemShare * ((double)freeB + held);
+    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return 0;   // the fixed defaults (wf_plan)
+    return kLaneMemShare * ((double)freeB + (double)held_lane_bytes(ctx));
 }
 
 // The frames of one render call.  One frame (pbr_hip_render): its chunks alternate over the lanes,
@@ -1393,6 +1329,7 @@ hipStream_t lane_stream(pbr_hip_ctx* ctx, hipStream_t s, int l) { return l ? ctx
 int wf_fork(pbr_hip_ctx* ctx, hipStream_t s, int lanes) {
     const bool own = PBR_OWN_LANES && lanes >= kWfLanes && s != ctx->stream;
     ctx->lane0 = own ? ctx->stream : s;
+    ctx->lastOwnLane0 = own;
     if (lanes < 2) return PBR_OK;
     if (int rc = create_lane_streams(ctx)) return rc;
     HIP_TRY(hipEventRecord(ctx->evFork, s));
@@ -1407,16 +1344,19 @@ int wf_join(pbr_hip_ctx* ctx, hipStream_t s, int lanes) {
     }
     return PBR_OK;
 }
-// A batch: frame f's chunks ended on the lanes in `used` (bit mask; lane 0 is `s`): one event per
-// lane, recorded after the lane's last launch of the frame (pbr_hip_wait_frame waits on them).
+// A batch: the end of frame f, as events pbr_hip_wait_frame waits on.  used == 0: the frame's lanes
+// were joined back into `s` (wf_join), or it ran on `s` alone (the megakernel): one event on `s`, which
+// is behind every lane — not on lane 0's stream, which with four lanes is the context's stream and
+// has waited for no other lane.  Otherwise (the rotation goes on without a join) the frame's chunks
+// ended on the lanes in `used` (bit mask): one event per lane, after the lane's last launch of the frame.
 int wf_frame_done(pbr_hip_ctx* ctx, hipStream_t s, int f, unsigned used) {
     if ((int)ctx->frameEv.size() <= f) ctx->frameEv.resize(f + 1);
     pbr_hip_ctx::FrameEv& e = ctx->frameEv[f];
-    e.used = used;
+    e.used = used ? used : 1u;
     for (int l = 0; l < kWfLanes; ++l) {
-        if (!(used & (1u << l))) continue;
+        if (!(e.used & (1u << l))) continue;
         if (!e.ev[l]) HIP_TRY(hipEventCreateWithFlags(&e.ev[l], hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(e.ev[l], lane_stream(ctx, s, l)));
+        HIP_TRY(hipEventRecord(e.ev[l], used ? lane_stream(ctx, s, l) : s));
     }
     return PBR_OK;
 }
@@ -1478,34 +1418,28 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
     // one SkyBox light: its radiance is looked up by the shadow kernel (k_wf_shade)
     const bool skyDeferred = !ml && ctx->host.lights[0].type == LT_SKY;
     const bool skyHalton = skyDeferred && P.smp.type == PBR_SAMPLER_HALTON;   // the SkyBox shade variants (C2)
-    // records per sample and level: A, F+cos, pdf (36 B) + per light 17 B; the chunk shrinks so
-    // they stay under 8 GB per lane (C2: 5 levels × 36 B × 2^25 = 6 GB)
-    int maxLog2 = 25;
-    while (maxLog2 > 20 && (double)levels * (36.0 + (ml ? 17.0 * nL : 0.0)) * (double)(1LL << maxLog2) > 8e9) --maxLog2;
-    const int lightsPerShade = ml ? std::max(1, nL) : 1;
-    // the lane buffers below, per sample: two ray queues, the shadow queue(s), the records
-    const double bytesPerSample = 2 * 52.0 + (52.0 + (skyDeferred ? 16.0 : 0.0)) * lightsPerShade + 16.0 +
-                                  levels * (36.0 + (ml ? 17.0 * nL : 0.0)) + 8.0;
-    const WfChunks ch = wf_chunks(ctx->sched, P, PBR_WF_WHITTED_MAXLOG2, F.batch, bytesPerSample, lane_budget(ctx), maxLog2);
-    const size_t cap = ch.cap, qcap = ch.qcap;
-    const size_t sqcap = qcap * (size_t)lightsPerShade;   // shadow-queue entries
+    const int lightsPerShade = whitted_lights_per_shade(nL);
     const int lobes = scene_lobe_kinds(ctx->host);
     const bool simple = (lobes & ~kSimpleLobes) == 0;
     const bool mm = (lobes & ~kMatteMirrorLobes) == 0;   // Lambert + mirror only (C2)
     const bool textured = (lobes & kTexturedLobes) != 0;
     const bool matsLds = ctx->host.materials.size() <= (size_t)kLdsMats;   // templates staged in LDS
-    // The level-0 shade traces its own camera rays (no camera kernel and queue).  Frames with fewer
-    // chunks than lanes (rank shards of a multi-GPU C2 job) keep the separate kernels by default:
-    // there the camera kernel's 8 waves per SIMD win (C2 shard 0/8, one chunk: 2.58 → 3.10 ms fused;
-    // shard 0/2, two chunks: 9.58-9.63 → 10.12-10.22).
-    // Round 6: a batch whose few-chunk frames rotate over the lanes (a rank's shard) fuses as well — its
-    // frames overlap on the lanes, which hides the fused kernel's lower occupancy: C2 8-rank shards
-    // 2.10-2.19 → 1.99-2.02 ms, 4-rank 4.13-4.31 → 3.95-4.01 (profiles/r6_shard_c2*.json).
-    const long long nChunks = (P.nPixels + ch.chunkPix - 1) / ch.chunkPix;
-    const int fuse = ctx->sched.fuse_camera;
-    const bool rotating = F.batch && nChunks < ch.lanes;
-    const bool fuseCamera = kPacket && kQuadTraversal && fuse != PBR_FUSE_OFF && (mm || simple) && matsLds && !textured &&
-                            !ml && (nChunks >= std::max(2, ch.lanes) || fuse == PBR_FUSE_ON || rotating);
+    // chunk size, lanes, queue capacities and the level-0 fusion: pbr_chunk_plan.h
+    WfPlanIn in;
+    in.integrator = PBR_INTEGRATOR_WHITTED;
+    in.nPixels = P.nPixels;
+    in.spp = spp;
+    in.maxDepth = P.maxDepth;
+    in.nLights = nL;
+    in.skyLight = skyDeferred;
+    in.batch = F.batch;
+    in.sceneFusable = kPacket && kQuadTraversal && (mm || simple) && matsLds && !textured;
+    in.laneBudget = lane_budget(ctx);
+    const WfChunks ch = ctx->lastPlan = wf_plan(ctx->sched, in);
+    const size_t cap = ch.cap, qcap = ch.qcap;
+    const size_t sqcap = qcap * (size_t)lightsPerShade;   // shadow-queue entries
+    const long long nChunks = ch.nChunks;
+    const bool fuseCamera = ch.fuseCamera;
     // + pass-through levels only when some primitive has no material (Whitted's no-BSDF branch)
     const int maxLevels = levels;   // no material-less primitives here (those scenes run the megakernel)
     // Shadow rays of level L run on a second stream, overlapping extend(L+1) and shade(L+1) (they
@@ -1683,7 +1617,7 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
         prof_host(ctx, KP_WF_FINISH, 1, (unsigned long long)W.nSamples);
     }
     if (!rotate) { if (int rc = wf_join(ctx, s, ch.lanes)) return rc; }
-    if (F.batch) { if (int rc = wf_frame_done(ctx, s, f, rotate ? used : 1u)) return rc; }
+    if (F.batch) { if (int rc = wf_frame_done(ctx, s, f, rotate ? used : 0u)) return rc; }
     }
     HIP_TRY(hipGetLastError());
     return rotate ? wf_join(ctx, s, ch.lanes) : PBR_OK;
@@ -1692,18 +1626,19 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
 // Wavefront Path: per bounce shade → shadow → probe → resolve → extend (pbr_wavefront_path.h).
 int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol, const FrameSet& F) {
     const int spp = P.spp;
-    // ≈ 290 B of queues + state per sample: 19.5 GB per 2^26 chunk and lane.  Measured (bit-identical):
-    // C3 2^25 349.4 ms, 2^26 336.1, 2^27 340.4; C5 2^25 1979 ms, 2^26 1939, 2^27 1919
-    // the lane buffers below, per sample: two ray queues with their state (84 B each), shadow and probe
-    // queues, the direct records, the sample's L and index (+ VolPath's transmittance walk and
-    // records), and the class pass lists (at most 5 passes)
-    // Path: four lanes where four lanes of 2^27-sample chunks fit the budget (bit-identical, 2^27
-    // chunks, frame ms in batches: C3 204.5 → 195.8, C4 4217 → 4160; VolPath's four lanes would have to
-    // drop to 2^26 chunks: C5 776.6 → 806.0, profiles/r6_lanes4_batch.log)
-    const WfChunks ch = wf_chunks(ctx->sched, P, 27, F.batch, (vol ? 460.0 : 340.0) + 4.0 * 5, lane_budget(ctx), 0, 20,
-                                  vol ? 0 : 4);
+    // chunk size, lanes and queue capacities, with the bytes per sample of the lane buffers below and
+    // Path's four lanes: pbr_chunk_plan.h
+    WfPlanIn in;
+    in.integrator = vol ? PBR_INTEGRATOR_VOLPATH : PBR_INTEGRATOR_PATH;
+    in.nPixels = P.nPixels;
+    in.spp = spp;
+    in.maxDepth = P.maxDepth;
+    in.nLights = (int)ctx->host.lights.size();
+    in.batch = F.batch;
+    in.laneBudget = lane_budget(ctx);
+    const WfChunks ch = ctx->lastPlan = wf_plan(ctx->sched, in);
     const size_t cap = ch.cap, qcap = ch.qcap;
-    const long long nChunks = (P.nPixels + ch.chunkPix - 1) / ch.chunkPix;
+    const long long nChunks = ch.nChunks;
     const int lobes = scene_lobe_kinds(ctx->host);
     const bool simple = (lobes & ~kSimpleLobes) == 0;
     const bool micro = (lobes & ~kMicroLobes) == 0;   // Lambert + microfacet reflection/transmission (C4, C5)
@@ -1958,7 +1893,7 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
         prof_host(ctx, KP_WFP_FINISH, 1, (unsigned long long)W.nSamples);
     }
     if (!rotate) { if (int rc = wf_join(ctx, s, ch.lanes)) return rc; }
-    if (F.batch) { if (int rc = wf_frame_done(ctx, s, f, rotate ? used : 1u)) return rc; }
+    if (F.batch) { if (int rc = wf_frame_done(ctx, s, f, rotate ? used : 0u)) return rc; }
     }
     HIP_TRY(hipGetLastError());
     return rotate ? wf_join(ctx, s, ch.lanes) : PBR_OK;
@@ -2432,6 +2367,11 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
     if (blocks > 0x7fffffffLL) return set_err(ctx, PBR_E_UNSUPPORTED, "frame too large");
     dim3 grid((unsigned)blocks), block(256);
     HIP_TRY(hipEventRecord(ctx->ev0, s));
+    // per-call state of the lanes: lane 0 is the caller's stream unless this call's wf_fork moves it (a
+    // call that forks nothing — the megakernel — must not inherit the stream an earlier call chose)
+    ctx->lane0 = s;
+    ctx->lastOwnLane0 = false;
+    ctx->lastPlan = wf_no_chunks();
     if (blocks > 0) {
         bool st = d->collect_stats != 0;
         // (a tree too deep for the quad walk's stack runs the megakernel's binary walk)
@@ -2470,7 +2410,7 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
                     });
                 prof_host(ctx, KP_MEGA, 0, (unsigned long long)npx * (unsigned long long)spp);
                 prof_host(ctx, KP_MEGA, 1, (unsigned long long)npx);
-                if (F.batch) { if (int rc = wf_frame_done(ctx, s, f, 1u)) return rc; }
+                if (F.batch) { if (int rc = wf_frame_done(ctx, s, f, 0u)) return rc; }
             }
         }
 #undef PBR_LAUNCH
@@ -2561,20 +2501,68 @@ int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f) {
     return PBR_OK;
 }
 
+// What is wrong with a schedule request (nullptr: nothing).
+static const char* schedule_error(const pbr_schedule& s) {
+    if (s.kernels != PBR_KERNELS_AUTO && s.kernels != PBR_KERNELS_MEGAKERNEL) return "schedule: unknown kernels mode";
+    if (s.chunk_log2 != 0 && (s.chunk_log2 < 10 || s.chunk_log2 > 28)) return "schedule: chunk_log2 must be 0 or 10..28";
+    if (s.lanes < 0 || s.lanes > kWfLanes) return "schedule: lanes must be 0..4";
+    if (s.fuse_camera < PBR_FUSE_AUTO || s.fuse_camera > PBR_FUSE_ON) return "schedule: unknown fuse mode";
+    if (s.serial != 0 && s.serial != 1) return "schedule: serial must be 0 or 1";
+    return nullptr;
+}
+
 int pbr_hip_set_schedule(pbr_hip_ctx* ctx, const pbr_schedule* sched) {
     if (!ctx) return PBR_E_INVALID;
     pbr_schedule s = {};
     if (sched) s = *sched;
-    if (s.kernels != PBR_KERNELS_AUTO && s.kernels != PBR_KERNELS_MEGAKERNEL)
-        return set_err(ctx, PBR_E_INVALID, "schedule: unknown kernels mode");
-    if (s.chunk_log2 != 0 && (s.chunk_log2 < 10 || s.chunk_log2 > 28))
-        return set_err(ctx, PBR_E_INVALID, "schedule: chunk_log2 must be 0 or 10..28");
-    if (s.lanes < 0 || s.lanes > kWfLanes) return set_err(ctx, PBR_E_INVALID, "schedule: lanes must be 0..4");
-    if (s.fuse_camera < PBR_FUSE_AUTO || s.fuse_camera > PBR_FUSE_ON) return set_err(ctx, PBR_E_INVALID, "schedule: unknown fuse mode");
-    if (s.serial != 0 && s.serial != 1) return set_err(ctx, PBR_E_INVALID, "schedule: serial must be 0 or 1");
+    if (const char* what = schedule_error(s)) return set_err(ctx, PBR_E_INVALID, what);
     HIP_TRY(hipSetDevice(ctx->device));
     if (int rc = drain(ctx)) return rc;   // an asynchronous frame may still use the lane buffers
     ctx->sched = s;
+    return PBR_OK;
+}
+
+static void fill_chunk_plan(const WfChunks& c, pbr_chunk_plan* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->lanes = c.lanes;
+    out->chunk_log2 = c.chunkLog2;
+    out->chunk_pixels = c.chunkPix;
+    out->n_chunks = c.nChunks;
+    out->cap = c.cap;
+    out->qcap = c.qcap;
+    out->seg_cap = c.segCap;
+    out->fused_camera = c.fuseCamera ? 1 : 0;
+    out->bytes_per_sample = c.bytesPerSample;
+    out->lane_budget = c.budget;
+}
+
+int pbr_hip_plan_chunks(const pbr_schedule* sched, const pbr_chunk_query* q, pbr_chunk_plan* out) {
+    if (!q || !out) return PBR_E_INVALID;
+    pbr_schedule s = {};
+    if (sched) s = *sched;
+    if (schedule_error(s)) return PBR_E_INVALID;
+    if (q->integrator < PBR_INTEGRATOR_WHITTED || q->integrator > PBR_INTEGRATOR_VOLPATH) return PBR_E_INVALID;
+    if (q->n_pixels < 1 || q->spp < 1 || q->n_lights < 0 || !(q->lane_budget >= 0)) return PBR_E_INVALID;
+    WfPlanIn in;
+    in.integrator = q->integrator;
+    in.nPixels = q->n_pixels;
+    in.spp = q->spp;
+    in.maxDepth = q->max_depth;
+    in.nLights = q->n_lights;
+    in.skyLight = q->sky_light != 0;
+    in.batch = q->batch != 0;
+    in.sceneFusable = q->scene_fusable != 0;
+    in.laneBudget = q->lane_budget;
+    fill_chunk_plan(wf_plan(s, in), out);
+    return PBR_OK;
+}
+
+int pbr_hip_last_chunks(pbr_hip_ctx* ctx, pbr_chunk_plan* out) {
+    if (!ctx) return PBR_E_INVALID;
+    if (!out) return set_err(ctx, PBR_E_INVALID, "last_chunks: out == NULL");
+    fill_chunk_plan(ctx->lastPlan, out);
+    out->lane0_on_ctx_stream = ctx->lastOwnLane0 ? 1 : 0;
+    out->held_lane_bytes = held_lane_bytes(ctx);
     return PBR_OK;
 }
 

@@ -27,6 +27,7 @@ constexpr int kWfMaxDepth = 16;   // Whitted levels of the wavefront schedule (d
 #endif
 constexpr int kWfBlocks = PBR_WF_BLOCKS;   // workgroups of the queue kernels = segments of a queue
 static_assert(kWfBlocks % 256 == 0, "the segment scan reads kWfBlocks / 256 counts per thread");
+static_assert(kWfBlocks == kWfPlanBlocks, "pbr_chunk_plan.h sizes the queue segments for these workgroups");
 
 // Per-kernel profile (pbr_hip_set_profiling): kernel families and their work counters
 // [kind * kProfFields + field].  Field 0 counts the units a family processed, fields 1..4 the

@@ -213,26 +213,28 @@ def frame_cases():
     return out
 
 
-def default_chunk_starts(n_pixels, spp, integrator, max_depth, lanes=3):
-    """First packed pixel of every chunk of the default wavefront schedule for a one-tile frame —
-    wf_chunks (pysicalbasedraytracer_amd/csrc/pbr_kernels.hip, `WfChunks wf_chunks`): at most 2^25
-    samples per Whitted chunk (fewer while levels x 36 B x 2^k > 8 GB), 2^26 for Path/VolPath; 24 or
-    more chunks are equalised to a whole number per lane.  Parity tests pick the pixels either side
-    of each boundary, where one lane's chunk hands over to the next."""
-    if integrator == capi.INTEGRATOR_WHITTED:
-        log2 = 25
-        while log2 > 20 and max(1, max_depth) * 36.0 * (1 << log2) > 8e9:
-            log2 -= 1
-    else:
-        log2 = 26
-    chunk = max(1, (1 << log2) // spp)
-    if chunk >= n_pixels:
-        return [0]
-    n = (n_pixels + chunk - 1) // chunk
-    if n >= 24:
-        n = max(lanes, n // lanes * lanes)
-        chunk = (n_pixels + n - 1) // n
-    return list(range(0, n_pixels, chunk))
+# The lane budget of an otherwise idle MI355X, for the tests that pin the documented plans: the
+# library gives its lanes kLaneMemShare = 3/4 (pbr_kernels.hip, lane_budget) of the device memory that
+# is free or already held by the context's lanes, and the device has 288 GB of HBM — 288e9 bytes at
+# the least (hipMemGetInfo reports 288 GiB = 309e9 less the runtime's own reservations).  The plans
+# pinned at this budget have room to spare: the largest, Path's four lanes of 2^27-sample chunks at
+# 360 B per sample and VolPath's three at 480 B, take 193.3e9 bytes.
+NOMINAL_LANE_BUDGET = 0.75 * 288e9
+
+
+def scene_plan(scene, rd, n_pixels=None, batch=False, lane_budget=NOMINAL_LANE_BUDGET, schedule=None):
+    """pbr_hip_plan_chunks for a frame of rd over the scene (n_pixels: default the whole raster): the
+    library's own chunk plan — lanes, chunk_pixels, n_chunks, ... — with no GPU call."""
+    lights = scene.lights
+    return capi.plan_chunks(rd.integrator, n_pixels or rd.camera.width * rd.camera.height, rd.spp, rd.max_depth,
+                            n_lights=len(lights), sky_light=len(lights) == 1 and lights[0].type == capi.LIGHT_SKYBOX,
+                            batch=batch, lane_budget=lane_budget, schedule=schedule)
+
+
+def chunk_starts(plan, n_pixels):
+    """First packed pixel of every chunk of a plan.  Parity tests pick the pixels either side of each
+    boundary, where one lane's chunk hands over to the next."""
+    return list(range(0, n_pixels, plan["chunk_pixels"]))
 
 
 def fullsize_pixels(width, height, n=1024, seed=0, boundaries=()):
@@ -286,8 +288,12 @@ def fullsize_cases():
                            ("c4", scenes.config_c4, 4), ("c5", scenes.config_c5, 5)):
         s, rd = fn(mesh=mesh)
         cam = rd.camera
-        starts = default_chunk_starts(cam.width * cam.height, rd.spp, rd.integrator, rd.max_depth)
-        tiles = fullsize_pixels(cam.width, cam.height, n=FULLSIZE_PIXELS, seed=seed, boundaries=starts[1:])
+        # the default schedule's boundaries on an idle device, and on one with half its memory taken
+        # (Path / VolPath then run chunks of half the size; a shared device decides which it is)
+        n = cam.width * cam.height
+        starts = sorted({p0 for budget in (NOMINAL_LANE_BUDGET, NOMINAL_LANE_BUDGET / 2)
+                         for p0 in chunk_starts(scene_plan(s, rd, lane_budget=budget), n)[1:]})
+        tiles = fullsize_pixels(cam.width, cam.height, n=FULLSIZE_PIXELS, seed=seed, boundaries=starts)
         out[name] = (s, scenes.render_desc(cam, rd.integrator, rd.spp, rd.max_depth, rd.rr_threshold,
                                            rd.light_strategy, capi.SAMPLER_HALTON, tiles=tiles))
     return out

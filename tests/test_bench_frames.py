@@ -1,12 +1,14 @@
 """Dense parity of the BENCHMARKED frames, through the path bench.py times (bench.py `frames`):
 the BASELINE configs' own scenes (scenes.CONFIGS) rendered as one pbr_hip_render_frames batch of two
 frames, asynchronously into device buffers on a caller stream, under the default schedule (chunks
-over three lanes, the fused level-0 Whitted shade, the classed Path/VolPath shades) — then compared
+over three lanes — four for Path, lane 0 then on the context's stream — the fused level-0 Whitted
+shade, the classed Path/VolPath shades) — then compared
 with the oracle (the CPU restatement of SamplerIntegrator::Render, Integrator.cpp:286-344):
 
 - C2 (1920x1080, 64 spp, Whitted): EVERY pixel, float colObj/spp and RGBA8, bit for bit;
 - C3 (Sobol), C4 (3840x2160x1024) and C5: a seeded 1/64 of the pixels plus both pixels either side
-  of every chunk boundary of the default schedule (where one lane's chunk hands over to the next),
+  of every chunk boundary of the plan the device ran (pbr_hip_last_chunks: where one lane's chunk
+  hands over to the next; on an otherwise idle device C4's are multiples of 129,600 px),
   float colObj/spp and RGBA8 bit for bit (the share is printed: profiles/r6_gpu_tests.log);
 - the batch's second frame equal to the first over the whole raster, bit for bit.
 
@@ -21,7 +23,7 @@ import torch
 
 import oracle_lib as O
 from parity import assert_parity
-from ref_scenes import default_chunk_starts
+import ref_scenes as RS
 from pysicalbasedraytracer_amd import HipRenderer, scenes
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +41,9 @@ def hip():
 
 
 def bench_batch(hip, config, nframes=2):
-    """bench.py's timed window for one config: an nframes batch on a caller stream, device outputs."""
+    """bench.py's timed window for one config: an nframes batch on a caller stream, device outputs.
+    Also returns the chunk plan the device ran (pbr_hip_last_chunks) — whatever memory a shared
+    device had free."""
     s, rd = scenes.CONFIGS[config]()
     W, H = rd.camera.width, rd.camera.height
     full = scenes.render_desc(rd.camera, rd.integrator, rd.spp, rd.max_depth, rd.rr_threshold, rd.light_strategy,
@@ -52,27 +56,35 @@ def bench_batch(hip, config, nframes=2):
     rgbas = [torch.zeros((W * H, 4), dtype=torch.uint8, device=dev) for _ in range(nframes)]
     t0 = time.time()
     hip.render_frames(full, [t.data_ptr() for t in rgbs], [t.data_ptr() for t in rgbas], stream=stream.cuda_stream)
+    plan = hip.last_chunks()
     hip.sync()
     stream.synchronize()
     gpu_s = time.time() - t0
-    return s, rd, rgbs, rgbas, gpu_s
+    starts = RS.chunk_starts(plan, W * H)
+    print(f"{config} ran {plan}; chunks start at {starts[:4]}{' ...' if len(starts) > 4 else ''}")
+    assert len(starts) == plan["n_chunks"]
+    return s, rd, rgbs, rgbas, gpu_s, plan
 
 
-def picked_pixels(W, H, rd, seed):
-    """A seeded 1/64 of the packed (row-major) pixels, plus both sides of every chunk boundary."""
+def picked_pixels(W, H, plan, seed):
+    """A seeded 1/64 of the packed (row-major) pixels, plus both sides of every chunk boundary of the
+    plan the device ran."""
     n = W * H
     rng = np.random.default_rng(seed)
     picks = set(rng.choice(n, n // 64, replace=False).tolist())
-    for p0 in default_chunk_starts(n, rd.spp, rd.integrator, rd.max_depth)[1:]:
+    for p0 in RS.chunk_starts(plan, n)[1:]:
         picks.update((p0 - 1, p0))
     picks.update((0, n - 1))
     return np.array(sorted(picks), dtype=np.int64)
 
 
 def test_c2_whole_frame_batch_equals_oracle(hip):
-    s, rd, rgbs, rgbas, gpu_s = bench_batch(hip, "C2")
+    s, rd, rgbs, rgbas, gpu_s, plan = bench_batch(hip, "C2")
     W, H = rd.camera.width, rd.camera.height
-    assert len(default_chunk_starts(W * H, rd.spp, rd.integrator, rd.max_depth)) == 4   # 4 chunks, 3 lanes, fused level 0
+    # 4 chunks, 3 lanes, fused level 0 (Whitted's chunk does not depend on the free memory of a device
+    # with room for 37 GB of lane buffers)
+    assert (plan["n_chunks"], plan["lanes"], plan["fused_camera"]) == (4, 3, True), plan
+    assert RS.scene_plan(s, rd, batch=True)["n_chunks"] == 4
     t0 = time.time()
     c, c8, _ = O.render(s, scenes.render_desc(rd.camera, rd.integrator, rd.spp, rd.max_depth, rd.rr_threshold,
                                               rd.light_strategy, rd.sampler, tiles=[(0, 0, W, H)]))
@@ -90,14 +102,15 @@ def test_c2_whole_frame_batch_equals_oracle(hip):
 
 @pytest.mark.parametrize("config,seed", [("C3", 3), ("C4", 4), ("C5", 5)])
 def test_path_volpath_bench_batch_matches_oracle(hip, config, seed):
-    s, rd, rgbs, rgbas, gpu_s = bench_batch(hip, config)
+    s, rd, rgbs, rgbas, gpu_s, plan = bench_batch(hip, config)
     W, H = rd.camera.width, rd.camera.height
+    assert plan["n_chunks"] >= 2 and plan["lanes"] >= 2, plan   # (the frame is cut, whatever the free memory)
     g0 = rgbs[0].cpu().numpy()
     assert np.isfinite(g0).all() and (g0 >= 0).all()
     # the batch's frames are the same bits (the classed shades reorder queue entries across launches)
     assert np.array_equal(rgbs[1].cpu().numpy().view(np.uint32), g0.view(np.uint32))
     assert torch.equal(rgbas[1], rgbas[0])
-    picks = picked_pixels(W, H, rd, seed)
+    picks = picked_pixels(W, H, plan, seed)
     tiles = [(int(p % W), int(p // W), int(p % W) + 1, int(p // W) + 1) for p in picks]
     rdt = scenes.render_desc(rd.camera, rd.integrator, rd.spp, rd.max_depth, rd.rr_threshold, rd.light_strategy,
                              rd.sampler, tiles=tiles)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from lane_schedules import assert_regime, four_lanes
 from parity import assert_parity
 from pysicalbasedraytracer_amd import HipRenderer, assemble, capi, scenes, tile_grid
 
@@ -389,6 +390,37 @@ def test_sobol_caller_matrices_and_pow2_spp(hip):
 SCHEDULES = {"one_chunk": {}, "c12_3lanes": {"chunk_log2": 12, "lanes": 3},
              "c10_balanced": {"chunk_log2": 10, "lanes": 3}, "c12_2lanes": {"chunk_log2": 12, "lanes": 2},
              "c12_serial": {"chunk_log2": 12, "serial": 1}}   # serial: bench.py's standalone per-kernel window
+# Four lanes, each on its own queue (lane_schedules.py): 2^12-sample chunks make 11 (Path) and 8
+# (VolPath) chunks, 2^15 2 and 1, 2^10 41 → 40 and 29 → 28.
+FOUR_LANES = four_lanes(more=12, rotating=15, balanced=10)
+SCHEDULES.update({name: kw for name, (kw, _) in FOUR_LANES.items()})
+
+
+def wavefront_equals_megakernel(hip, rd, sched):
+    """The frame under SCHEDULES[sched] and under the megakernel: the same bits.  The four-lane
+    schedules also render asynchronously into NaN-filled device buffers, on a caller's stream (lane 0
+    then runs on the context's stream) and on the context's own, in the regime they are named for."""
+    import torch
+    hip.set_schedule(kernels=capi.KERNELS_MEGAKERNEL)
+    mk, mk8, _ = hip.render(rd)
+    hip.set_schedule(**SCHEDULES[sched])
+    wf, wf8, _ = hip.render(rd)
+    assert np.array_equal(wf.view(np.uint32), mk.view(np.uint32)), float(np.abs(wf - mk).max())
+    assert np.array_equal(wf8, mk8)
+    if sched not in FOUR_LANES:
+        return
+    dev = torch.device("cuda", 0)
+    npx = HipRenderer.n_pixels(rd)
+    for stream in (torch.cuda.Stream(dev), None):
+        rgb = torch.full((npx, 3), float("nan"), dtype=torch.float32, device=dev)
+        rgba = torch.zeros((npx, 4), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()   # (the fills run on torch's stream, the frame on its own)
+        hip.render_device(rd, rgb.data_ptr(), rgba.data_ptr(), stream=stream.cuda_stream if stream else None, sync=False)
+        assert_regime(hip.last_chunks(), FOUR_LANES[sched][1], caller_stream=stream is not None, batch=False)
+        hip.sync()
+        torch.cuda.synchronize()
+        assert np.array_equal(rgb.cpu().numpy().view(np.uint32), mk.reshape(npx, 3).view(np.uint32)), stream
+        assert np.array_equal(rgba.cpu().numpy(), mk8.reshape(npx, 4)), stream
 
 
 @pytest.mark.parametrize("sched", sorted(SCHEDULES))
@@ -406,12 +438,7 @@ def test_wavefront_path_equals_megakernel(hip, config, sched):
             rd = scenes.render_desc(rd.camera, rd.integrator, rd.spp, rd.max_depth, rd.rr_threshold,
                                     capi.LIGHTS_POWER, capi.SAMPLER_HALTON)
     hip.upload(s)
-    hip.set_schedule(**SCHEDULES[sched])
-    wf, wf8, _ = hip.render(rd)
-    hip.set_schedule(kernels=capi.KERNELS_MEGAKERNEL)
-    mk, mk8, _ = hip.render(rd)
-    assert np.array_equal(wf.view(np.uint32), mk.view(np.uint32)), float(np.abs(wf - mk).max())
-    assert np.array_equal(wf8, mk8)
+    wavefront_equals_megakernel(hip, rd, sched)
 
 
 @pytest.mark.parametrize("sched", sorted(SCHEDULES))
@@ -421,12 +448,7 @@ def test_wavefront_volpath_equals_megakernel(hip, sched):
     and as many chunks over two or three lanes."""
     s, rd = scenes.config_c5(80, 45, 8, mesh=small_dragon(40))
     hip.upload(s)
-    hip.set_schedule(**SCHEDULES[sched])
-    wf, wf8, _ = hip.render(rd)
-    hip.set_schedule(kernels=capi.KERNELS_MEGAKERNEL)
-    mk, mk8, _ = hip.render(rd)
-    assert np.array_equal(wf.view(np.uint32), mk.view(np.uint32)), float(np.abs(wf - mk).max())
-    assert np.array_equal(wf8, mk8)
+    wavefront_equals_megakernel(hip, rd, sched)
 
 
 def test_async_device_frames(hip):

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import oracle_lib as O
+from lane_schedules import assert_regime, four_lanes
 from pysicalbasedraytracer_amd import HipRenderer, ProgressiveRender, capi, scenes, tiles_for_rank
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,16 @@ SCHEDULES = {
     "serial": {"chunk_log2": 12, "serial": True},
     "megakernel": {"kernels": capi.KERNELS_MEGAKERNEL},
 }
+# Four lanes, each on its own queue (lane_schedules.py).  A pass of 2 samples per pixel is 18,432 /
+# 4,608 / 10,368 / 7,200 samples (whitted, whitted_lights, path, volpath): 2^10-sample chunks make 18 /
+# 5 / 11 / 8 of them, 2^13 3 / 1 / 2 / 1 (the passes rotate, ordered by pass_order's events).  24 chunks
+# need 24,576 samples in a pass: Whitted's passes of 4 samples have 36, Path's and VolPath's one pass
+# of 8 has 41 → 40 and 29 → 28; the 64x36 multi-light frame cannot have 24 at all.
+FOUR_LANES = four_lanes(more=10, rotating=13, balanced=10)
+SCHEDULES.update({name: kw for name, (kw, _) in FOUR_LANES.items()})
+PASS_LAYOUT = {(kind, name): ((4, 2) if kind == "whitted" else (8, 1)) if name == "l4_balanced" else (2, 4)
+               for kind in SCENES for name in SCHEDULES}   # (samples per pass, passes)
+del PASS_LAYOUT[("whitted_lights", "l4_balanced")]
 
 _scene_cache, _oracle_cache = {}, {}
 
@@ -95,22 +106,27 @@ def check(key, s, rd, k, rgb, rgba, what=""):
 
 
 # ------------------------------------------------------------------ 1. parity per pass
-@pytest.mark.parametrize("sched", sorted(SCHEDULES))
-@pytest.mark.parametrize("kind", sorted(SCENES))
+@pytest.mark.parametrize("kind,sched", sorted(PASS_LAYOUT), ids=lambda v: v)
 def test_every_pass_equals_the_oracle_at_its_sample_count(hip, kind, sched):
+    """Four passes of 2 samples (the balanced four-lane schedule: PASS_LAYOUT), on a caller's stream;
+    the four-lane schedules on the context's own stream as well, in the regime they are named for."""
     s, rd = scene(kind)
+    per_pass, n = PASS_LAYOUT[(kind, sched)]
     hip.upload(s)
     hip.set_schedule(**SCHEDULES[sched])
-    stream = torch.cuda.Stream(DEV)
-    acc = new_accum(rd)
-    rgbs, rgbas = passes(hip, rd, 0, 2, 4, acc, stream)
-    hip.sync()
-    torch.cuda.synchronize()
-    for p in range(4):
-        check(kind, s, rd, 2 * (p + 1), rgbs[p], rgbas[p], f"pass {p}")
+    for stream in (torch.cuda.Stream(DEV), None) if sched in FOUR_LANES else (torch.cuda.Stream(DEV),):
+        acc = new_accum(rd)
+        torch.cuda.synchronize()   # (the NaN fills run on torch's stream, the passes on their own)
+        rgbs, rgbas = passes(hip, rd, 0, per_pass, n, acc, stream)
+        if sched in FOUR_LANES:
+            assert_regime(hip.last_chunks(), FOUR_LANES[sched][1], caller_stream=stream is not None, batch=True)
+        hip.sync()
+        torch.cuda.synchronize()
+        for p in range(n):
+            check(kind, s, rd, per_pass * (p + 1), rgbs[p], rgbas[p], f"pass {p}")
     ref, ref8, _ = hip.render(rd)
-    assert np.array_equal(bits(rgbs[3].cpu().numpy()), bits(ref))
-    assert np.array_equal(rgbas[3].cpu().numpy(), ref8)
+    assert np.array_equal(bits(rgbs[n - 1].cpu().numpy()), bits(ref))
+    assert np.array_equal(rgbas[n - 1].cpu().numpy(), ref8)
 
 
 @pytest.mark.parametrize("sched", ["default", "chunks_3_lanes"])

@@ -121,8 +121,10 @@ def test_device_matches_reference_fullsize(hip, name):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_production_schedule_matches_reference_fullsize(hip, name):
     """The frame exactly as bench.py renders it — the bench's own scene (scenes.CONFIGS), the whole
-    raster as one tile, the default schedule (C2: 4 chunks over 3 lanes with the fused level-0
-    shade; C3: 8 chunks; C4: 126 balanced chunks; C5: 16 chunks), asynchronous into device buffers
+    raster as one tile, the default schedule (on an idle device C2: 4 chunks over 3 lanes with the
+    fused level-0 shade; C3: 4 chunks on 4 lanes; C4: 64 balanced chunks on 4 lanes; C5: 8 chunks on
+    3 lanes; with half the memory taken, chunks of half the size — the fixture's pixels sit either
+    side of both sets of boundaries, ref_scenes.fullsize_cases), asynchronous into device buffers
     on a caller stream — and then the fixture's 1024 pixels picked out of it and held to the same
     gates against the reference as the one-pixel-tile renders above (Integrator.cpp:286-344).
     C3 runs on Halton here (the reference has no Sobol sampler, F3); its Sobol frame is checked
