@@ -754,6 +754,16 @@ class SamplerIntegrator : public Integrator {
     // custom (table) sampler throw.
     void RenderSamples(const Scene& scene, int firstSample, int nSamples);
     int SamplesDone() const { return samplesDone; }
+    // Adaptive sampling (no reference counterpart; pbr_hip_render_adaptive): every pixel takes minSamples
+    // samples, then rounds of samplesPerRound for the pixels whose error estimate — the variance of the
+    // pixel mean summed over the channels — still exceeds (tolerance × max(mean summed over the channels,
+    // floor))², up to the sampler's samplesPerPixel.  A pixel that passes the test once has stopped for
+    // good.  Fills m_FrameBuffer as RenderSamples does, every pixel with its image at its own count, and
+    // returns the sample map: the samples each pixel took, in the order of the tiles (SetTiles; none: the
+    // pixel bounds, row by row).  A tolerance of 0 renders every pixel with any variance to the budget
+    // (Render's bits there).  Synchronous, single device; a custom (table) sampler throws.  Starts a new
+    // image: a RenderSamples pass cannot continue it.
+    std::vector<int> RenderAdaptive(const Scene& scene, int minSamples, int samplesPerRound, float tolerance, float floor);
     // Uploads the scene to the integrator's device (BVHAccel build, lights, media); Render and Li
     // do it on first use.  The reference's SamplerIntegrator::Preprocess is a no-op hook.
     virtual void Preprocess(const Scene& scene, Sampler& sampler);
@@ -801,6 +811,7 @@ class SamplerIntegrator : public Integrator {
     struct Progressive;                  // RenderSamples: the carried sums and the pass's images, on the device
     std::shared_ptr<Progressive> prog;
     int samplesDone = 0;
+    std::vector<int> RenderPass(const Scene& scene, const char* who, int firstSample, int nSamples, const pbr_adaptive* adaptive);
 };
 class WhittedIntegrator : public SamplerIntegrator {   // Integrator/WhittedIntegrator.h
   public:

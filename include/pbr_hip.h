@@ -19,7 +19,9 @@
  *                           drives {Whitted,Path,VolPath}Integrator::Li per sample
  *   pbr_hip_render_passes — (none; the reference renders whole frames): that Render's sample loop in
  *                           resumable passes over a carried per-pixel sum (progressive rendering)
- *   pbr_hip_destroy       — scene/integrator destructors
+ *   pbr_hip_render_adaptive — (none): those passes with a per-pixel stopping rule (adaptive sampling;
+ *                           pbr_hip_adaptive_select and pbr_hip_render_passes_list are its two steps)
+ *   pbr_hip_destroy      — scene/integrator destructors
  *   pbr_hip_last_error    — (none; the reference fails silently)
  *   pbr_hip_sync          — (none; the reference's Render returns when the frame is done): waits
  *                           for asynchronous frames and reports a deferred failure
@@ -344,6 +346,65 @@ int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f);
  * p) orders another stream after pass p of the last call. */
 int pbr_hip_render_passes(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int first_sample, int samples_per_pass,
                           int n_passes, float* accum, float* const* rgb_outs, uint8_t* const* rgba_outs);
+
+/* ---- adaptive sampling (no reference counterpart) ----
+ * Per-pixel stopping over the accumulator of pbr_hip_render_passes.  The rule, for a pixel with k >= 2
+ * samples done and sums S_c = Σ L_c, Q_c = Σ L_c² (c = r, g, b), every operation in float32, in this
+ * order, nothing fused:
+ *     n = (float)k;   m_c = S_c / n;   d_c = Q_c - S_c * m_c;   v_c = d_c > 0 ? d_c : 0   (NaN: 0)
+ *     E = ((v_r + v_g) + v_b) / (n * (n - 1))        variance of the pixel mean, summed over channels
+ *     M = (m_r + m_g) + m_b;   B = M > floor ? M : floor;   T = tolerance * B
+ *     active = E > T * T                              (any NaN: not active)
+ * There is no square root and no transcendental in it, so a float32 restatement on the host decides
+ * exactly as the device does.  A pixel that is not active has stopped for good.
+ *
+ * pbr_hip_adaptive_select evaluates the rule over the n_in pixels of list_in (device; ascending packed
+ * pixel indices; NULL: all n_pixels, n_in ignored) from accum (device, 6 floats per frame pixel) and
+ * writes the active ones, in the same ascending order, to list_out (device, room for as many entries as
+ * were considered; not list_in itself) and their number to *n_out (host).  err_out (device, one float per
+ * frame pixel, or NULL) receives E of every pixel considered; other entries are not written.  Waits for
+ * renders in flight on the context, and is synchronous: it returns *n_out.  PBR_E_INVALID:
+ * samples_done < 2, n_pixels outside [1, 2^31), a negative or NaN tolerance or floor, NULL accum, list_out
+ * or n_out. */
+int pbr_hip_adaptive_select(pbr_hip_ctx* ctx, int64_t n_pixels, int samples_done, float tolerance, float floor, const float* accum,
+                            const int32_t* list_in, int n_in, int32_t* list_out, int* n_out, float* err_out);
+/* One pass of `samples` samples, numbered from first_sample, for the n_list listed pixels only: list =
+ * device, strictly ascending indices into the descriptor's packed tile order (checked on the device:
+ * PBR_E_INVALID).  accum, rgb_out and rgba_out are whole-frame buffers in that order (either image may
+ * be NULL); a listed pixel ends with exactly what pbr_hip_render_passes would have left there, entries
+ * of unlisted pixels are not written.  The list is cut into runs — listed pixels consecutive in one row
+ * of one tile — which the pass renders as tiles over a dense copy of the listed sums; the call waits
+ * for the run count (one 8-byte copy; this also waits for work queued before it on the stream), then
+ * queues the pass as pbr_hip_render_passes does.  Conditions as there: outputs_on_device = 1, no stats,
+ * a sample table returns PBR_E_UNSUPPORTED, first_sample + samples within the budget.  n_list == 0 is
+ * PBR_OK and launches nothing.  pbr_hip_last_chunks reports the plan for n_list pixels;
+ * pbr_hip_wait_frame(ctx, stream, 0) orders another stream after the pass. */
+int pbr_hip_render_passes_list(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int first_sample, int samples, const int32_t* list,
+                               int n_list, float* accum, float* rgb_out, uint8_t* rgba_out);
+typedef struct pbr_adaptive {
+    int min_samples;        /* every pixel takes these first: 2 <= min_samples <= budget */
+    int samples_per_round;  /* what the pixels still active take per round, >= 1 */
+    float tolerance;        /* relative error of the pixel mean at which a pixel stops, >= 0 */
+    float floor;            /* lower bound of the mean the tolerance is relative to, >= 0 */
+} pbr_adaptive;
+typedef struct pbr_adaptive_result {
+    int rounds;             /* passes rendered, the full-frame first one included */
+    int max_samples_done;   /* the largest count any pixel reached */
+    int64_t samples;        /* Σ counts */
+    int64_t active_at_end;  /* pixels the last select still found active (they stopped at the budget) */
+} pbr_adaptive_result;
+/* A whole adaptive render; desc->spp is the budget (Sobol: rounded up to a power of two, as for passes).
+ * Every pixel takes min_samples samples (a plain full-frame pass); then, with k samples done by the
+ * pixels still listed: select over the list at k; stop if nothing is active or k is the budget; else the
+ * active pixels take min(samples_per_round, budget - k) more.  On return counts[p] (device, int32 per
+ * pixel) is the number of samples pixel p took, accum[p] its sums over exactly those samples, rgb_out[p]
+ * and rgba_out[p] (either may be NULL) its image at that count: the bits pbr_hip_render_passes leaves
+ * at that count.  A Sobol image at a count that is not a power of two has no reference counterpart; the
+ * call is allowed all the same.  Synchronous: each round waits for one 8-byte copy (active pixels, runs)
+ * before it queues the round's pass, and the call returns when the last round is done.  The library
+ * keeps no state between calls: a checkpoint is accum plus counts.  `result` may be NULL. */
+int pbr_hip_render_adaptive(pbr_hip_ctx* ctx, const pbr_render_desc* desc, const pbr_adaptive* params, float* accum, int32_t* counts,
+                            float* rgb_out, uint8_t* rgba_out, pbr_adaptive_result* result);
 
 /* ---- schedule (no reference counterpart) ----
  * How a frame is cut into launches on the device.  Every setting renders the same bits (the GPU

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi, scenes  # noqa: F401
 
-__all__ = ["HipRenderer", "ProgressiveRender", "capi", "scenes", "tile_grid", "tiles_for_rank"]
+__all__ = ["AdaptiveRender", "HipRenderer", "ProgressiveRender", "capi", "scenes", "tile_grid", "tiles_for_rank"]
 
 
 class PbrError(RuntimeError):
@@ -154,6 +154,101 @@ class HipRenderer:
         d.collect_stats = 0
         self._check(self.lib.pbr_hip_render_passes(self.ctx, C.byref(d), first_sample, samples_per_pass, n, accum_ptr,
                                                    rgb, rgba), "render_passes")
+
+    @staticmethod
+    def _check_rule(who, tolerance, floor):
+        tolerance, floor = float(tolerance), float(floor)
+        if not tolerance >= 0.0:   # (a NaN fails the comparison)
+            raise ValueError(f"{who}: tolerance must be >= 0, not {tolerance}")
+        if not floor >= 0.0:
+            raise ValueError(f"{who}: floor must be >= 0, not {floor}")
+        return tolerance, floor
+
+    def adaptive_select(self, n_pixels, samples_done, tolerance, floor, accum_ptr, list_out_ptr, list_in_ptr=None, n_in=0,
+                        err_out_ptr=None) -> int:
+        """The stopping rule of adaptive sampling over an accumulator (pbr_hip_adaptive_select): of the
+        n_in pixels in list_in (device int32, ascending; None: all n_pixels) those still active at
+        samples_done samples go, in order, to list_out (device int32); returns their number.  err_out
+        (device float32 per frame pixel) receives the error estimate E of the pixels considered.
+        Synchronous."""
+        n_pixels, samples_done, n_in = int(n_pixels), int(samples_done), int(n_in)
+        if samples_done < 2:
+            raise ValueError("adaptive_select: samples_done must be >= 2")
+        if n_pixels < 1 or n_pixels >= 1 << 31:
+            raise ValueError("adaptive_select: n_pixels must be in [1, 2^31)")
+        tolerance, floor = self._check_rule("adaptive_select", tolerance, floor)
+        if not accum_ptr or not list_out_ptr:
+            raise ValueError("adaptive_select: accum and list_out are required (device buffers)")
+        if list_in_ptr and not 0 <= n_in <= n_pixels:
+            raise ValueError(f"adaptive_select: n_in {n_in} outside [0, {n_pixels}]")
+        n = C.c_int(0)
+        self._check(self.lib.pbr_hip_adaptive_select(self.ctx, n_pixels, samples_done, tolerance, floor, accum_ptr,
+                                                     list_in_ptr or None, n_in, list_out_ptr, C.byref(n), err_out_ptr or None),
+                    "adaptive_select")
+        return n.value
+
+    def render_passes_list(self, rdesc, first_sample, samples, list_ptr, n_list, accum_ptr, rgb_ptr=None, rgba_ptr=None,
+                           stream: int | None = None):
+        """One pass of `samples` samples from sample number first_sample for the n_list pixels in list
+        (device int32, ascending packed pixel indices) only (pbr_hip_render_passes_list).  accum, rgb
+        and rgba are whole-frame device buffers; entries of unlisted pixels are not written.  Waits for
+        the list's run count, then queues the pass as render_passes does."""
+        first_sample, samples, n_list = int(first_sample), int(samples), int(n_list)
+        if samples < 1:
+            raise ValueError("render_passes_list: samples must be >= 1")
+        if first_sample < 0:
+            raise ValueError("render_passes_list: first_sample must be >= 0")
+        if n_list < 0 or n_list > self.n_pixels(rdesc):
+            raise ValueError(f"render_passes_list: n_list {n_list} outside [0, {self.n_pixels(rdesc)}]")
+        if n_list and not list_ptr:
+            raise ValueError("render_passes_list: list is required (a device buffer of int32 pixel indices)")
+        if not accum_ptr:
+            raise ValueError("render_passes_list: accum is required (a device buffer of 6 float32 per pixel)")
+        if rdesc.sampler == capi.SAMPLER_TABLE:
+            raise ValueError("render_passes_list: no passes over a sample table")
+        budget = self.sample_budget(rdesc)
+        if first_sample + samples > budget:
+            raise ValueError(f"render_passes_list: samples [{first_sample}, {first_sample + samples}) run past the budget "
+                             f"of {budget} samples per pixel")
+        d = type(rdesc).from_buffer_copy(rdesc)   # (the caller's descriptor is left as it was: render_frames)
+        d.outputs_on_device = 1
+        d.stream = stream
+        d.collect_stats = 0
+        self._check(self.lib.pbr_hip_render_passes_list(self.ctx, C.byref(d), first_sample, samples, list_ptr or None, n_list,
+                                                        accum_ptr, rgb_ptr or None, rgba_ptr or None), "render_passes_list")
+
+    @staticmethod
+    def _check_adaptive(who, rdesc, min_samples, samples_per_round, tolerance, floor):
+        if rdesc.sampler == capi.SAMPLER_TABLE:
+            raise ValueError(f"{who}: no passes over a sample table")
+        if rdesc.spp < 1:
+            raise ValueError(f"{who}: rdesc.spp (the sample budget) must be >= 1")
+        budget = HipRenderer.sample_budget(rdesc)
+        min_samples, samples_per_round = int(min_samples), int(samples_per_round)
+        if min_samples < 2 or min_samples > budget:
+            raise ValueError(f"{who}: min_samples {min_samples} outside [2, {budget}] (the budget)")
+        if samples_per_round < 1:
+            raise ValueError(f"{who}: samples_per_round must be >= 1")
+        tolerance, floor = HipRenderer._check_rule(who, tolerance, floor)
+        return capi.Adaptive(min_samples, samples_per_round, tolerance, floor)
+
+    def render_adaptive(self, rdesc, min_samples, samples_per_round, tolerance, floor, accum_ptr, counts_ptr, rgb_ptr=None,
+                        rgba_ptr=None, stream: int | None = None):
+        """A whole adaptive render (pbr_hip_render_adaptive): every pixel takes min_samples samples,
+        then rounds of samples_per_round for the pixels the stopping rule leaves active, up to the
+        budget rdesc.spp.  accum (6 float32 per pixel), counts (int32 per pixel), rgb, rgba: device
+        buffers.  Synchronous; returns the capi.AdaptiveResult."""
+        a = self._check_adaptive("render_adaptive", rdesc, min_samples, samples_per_round, tolerance, floor)
+        if not accum_ptr or not counts_ptr:
+            raise ValueError("render_adaptive: accum and counts are required (device buffers)")
+        d = type(rdesc).from_buffer_copy(rdesc)
+        d.outputs_on_device = 1
+        d.stream = stream
+        d.collect_stats = 0
+        res = capi.AdaptiveResult()
+        self._check(self.lib.pbr_hip_render_adaptive(self.ctx, C.byref(d), C.byref(a), accum_ptr, counts_ptr, rgb_ptr or None,
+                                                     rgba_ptr or None, C.byref(res)), "render_adaptive")
+        return res
 
     def wait_frame(self, stream: int | None, f: int):
         """Make `stream` wait for frame f of the last render_frames call, or pass f of the last
@@ -395,6 +490,119 @@ class ProgressiveRender:
         torch = self._buffers()
         self._accum.copy_(torch.from_numpy(np.ascontiguousarray(acc)))
         self.samples_done = done
+
+
+class AdaptiveRender:
+    """A render that stops each pixel once its estimated error is small enough (adaptive sampling).
+
+    Every pixel takes min_samples samples; then, round after round, the pixels whose error estimate —
+    the variance of the pixel mean summed over the channels — still exceeds (tolerance × max(mean summed
+    over the channels, floor))² take samples_per_round more, up to the budget rdesc.spp.  A pixel that
+    passes the test once has stopped for good.  Owns the accumulator ([n_pixels, 6] float32: Σ Li.rgb,
+    Σ Li.rgb²) and the per-pixel sample counts ([n_pixels] int32) as torch tensors on the renderer's
+    device, in the descriptor's packed tile order; a pixel's image is the bits of a whole render at the
+    pixel's count.  A checkpoint is those two tensors (state / restore)."""
+
+    def __init__(self, renderer: HipRenderer, rdesc, min_samples=4, samples_per_round=4, tolerance=0.02, floor=1e-3,
+                 device=None):
+        self.params = HipRenderer._check_adaptive("AdaptiveRender", rdesc, min_samples, samples_per_round, tolerance, floor)
+        self.renderer = renderer
+        self.rdesc = rdesc
+        self.budget = HipRenderer.sample_budget(rdesc)
+        self.n_pixels = HipRenderer.n_pixels(rdesc)
+        self.samples_done = 0      # the largest count any pixel has reached
+        self.rounds = 0            # passes rendered, the full-frame first one included
+        self.active = None         # pixels the last select found active (None: no select yet)
+        self._device = device
+        self._accum = self._counts = self._rgb = self._rgba = self._stream = None
+
+    def _buffers(self):
+        import torch
+        if self._accum is None:
+            dev = self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            self._accum = torch.zeros((self.n_pixels, 6), dtype=torch.float32, device=dev)
+            self._counts = torch.zeros((self.n_pixels,), dtype=torch.int32, device=dev)
+            self._rgb = torch.zeros((self.n_pixels, 3), dtype=torch.float32, device=dev)
+            self._rgba = torch.zeros((self.n_pixels, 4), dtype=torch.uint8, device=dev)
+            self._stream = torch.cuda.Stream(dev)   # (the library takes a real stream handle: ProgressiveRender)
+        return torch
+
+    def run(self, max_rounds=None):
+        """Runs to the end — nothing active, or the budget reached — and returns the (rgb, rgba) device
+        tensors.  A fresh render with max_rounds None is one pbr_hip_render_adaptive call.  With
+        max_rounds, at most that many passes are rendered (the full-frame first one counts) and run() may
+        be called again; this, and a run after restore(), drive the same rounds from here through
+        adaptive_select and render_passes_list, and leave the same bits.  Synchronous."""
+        if max_rounds is not None and int(max_rounds) < 1:
+            raise ValueError("AdaptiveRender.run: max_rounds must be >= 1")
+        torch = self._buffers()
+        torch.cuda.synchronize(self._accum.device)   # (the tensors' initialisation or restore)
+        r, p, st = self.renderer, self.params, self._stream.cuda_stream
+        if self.samples_done == 0 and max_rounds is None:
+            res = r.render_adaptive(self.rdesc, p.min_samples, p.samples_per_round, p.tolerance, p.floor,
+                                    self._accum.data_ptr(), self._counts.data_ptr(), self._rgb.data_ptr(),
+                                    self._rgba.data_ptr(), stream=st)
+            self.samples_done, self.rounds, self.active = res.max_samples_done, res.rounds, int(res.active_at_end)
+            return self._rgb, self._rgba
+        left = None if max_rounds is None else int(max_rounds)
+        if self.samples_done == 0:
+            r.render_passes(self.rdesc, 0, p.min_samples, self._accum.data_ptr(), [self._rgb.data_ptr()],
+                            [self._rgba.data_ptr()], stream=st)
+            r.sync()
+            self._counts.fill_(p.min_samples)
+            self.samples_done, self.rounds = p.min_samples, 1
+            left = None if left is None else left - 1
+        # the pixels still in the running are those at the largest count; each round selects over them
+        k = self.samples_done
+        cur = torch.nonzero(self._counts == k).flatten().to(torch.int32)
+        while left is None or left > 0:
+            nxt = torch.empty_like(cur)
+            torch.cuda.synchronize(self._accum.device)
+            n = r.adaptive_select(self.n_pixels, k, p.tolerance, p.floor, self._accum.data_ptr(), nxt.data_ptr(),
+                                  cur.data_ptr(), cur.numel()) if cur.numel() else 0
+            self.active = n
+            if n == 0 or k >= self.budget:
+                break
+            step = min(p.samples_per_round, self.budget - k)
+            cur = nxt[:n]
+            r.render_passes_list(self.rdesc, k, step, cur.data_ptr(), n, self._accum.data_ptr(), self._rgb.data_ptr(),
+                                 self._rgba.data_ptr(), stream=st)
+            r.sync()
+            k += step
+            self._counts[cur.long()] = k
+            self.samples_done, self.rounds = k, self.rounds + 1
+            left = None if left is None else left - 1
+        torch.cuda.synchronize(self._accum.device)
+        return self._rgb, self._rgba
+
+    def sample_map(self):
+        """The samples each pixel took so far: [n_pixels] int32 device tensor, packed tile order."""
+        self._buffers()
+        return self._counts
+
+    def state(self) -> dict:
+        """A checkpoint: the accumulator and the counts as numpy arrays (waits for the device)."""
+        self._buffers()
+        return {"accum": self._accum.cpu().numpy().copy(), "counts": self._counts.cpu().numpy().copy(), "rounds": self.rounds}
+
+    def restore(self, state: dict):
+        """Resume from state(): the same descriptor and parameters on any renderer holding the same
+        scene.  The images are not part of a checkpoint: a restored pixel's is written again by the
+        next pass that samples it."""
+        acc = np.asarray(state["accum"], dtype=np.float32)
+        cnt = np.asarray(state["counts"])
+        if acc.shape != (self.n_pixels, 6):
+            raise ValueError(f"AdaptiveRender.restore: accumulator of shape {acc.shape}, expected {(self.n_pixels, 6)}")
+        if cnt.shape != (self.n_pixels,):
+            raise ValueError(f"AdaptiveRender.restore: counts of shape {cnt.shape}, expected {(self.n_pixels,)}")
+        if cnt.size and (cnt.min() < 0 or cnt.max() > self.budget):
+            raise ValueError(f"AdaptiveRender.restore: counts outside the budget of {self.budget}")
+        torch = self._buffers()
+        self._accum.copy_(torch.from_numpy(np.ascontiguousarray(acc)))
+        self._counts.copy_(torch.from_numpy(np.ascontiguousarray(cnt.astype(np.int32))))
+        self.samples_done = int(cnt.max()) if cnt.size else 0
+        self.rounds = int(state.get("rounds", 0))
+        self.active = None
 
 
 # Edge of the multi-GPU tiles.  Per-rank frame of an 8-GPU C2 job (slowest of 8 ranks, one GPU,

@@ -187,6 +187,24 @@ class RenderDesc(C.Structure):
     ]
 
 
+class Adaptive(C.Structure):   # pbr_adaptive
+    _fields_ = [
+        ("min_samples", C.c_int),
+        ("samples_per_round", C.c_int),
+        ("tolerance", C.c_float),
+        ("floor", C.c_float),
+    ]
+
+
+class AdaptiveResult(C.Structure):   # pbr_adaptive_result
+    _fields_ = [
+        ("rounds", C.c_int),
+        ("max_samples_done", C.c_int),
+        ("samples", C.c_int64),
+        ("active_at_end", C.c_int64),
+    ]
+
+
 class RenderStats(C.Structure):
     _fields_ = [
         ("seconds", C.c_double),
@@ -277,6 +295,12 @@ EXPORTS = {
     "pbr_hip_wait_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "pbr_hip_render_passes": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "pbr_hip_adaptive_select": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "pbr_hip_render_passes_list": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbr_hip_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(AdaptiveResult)]),
     "pbr_hip_get_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int)]),
     "pbr_hip_sampler_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -319,7 +343,8 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_li", "pbr_hip_set_bvh_build", "pbr_hip_bvh_build_info", "pbr_hip_build_bvh",
                    "pbr_hip_set_schedule", "pbr_hip_sample_index", "pbr_hip_sample_dimensions",
                    "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk",
-                   "pbr_hip_plan_chunks", "pbr_hip_last_chunks")
+                   "pbr_hip_plan_chunks", "pbr_hip_last_chunks", "pbr_hip_adaptive_select", "pbr_hip_render_passes_list",
+                   "pbr_hip_render_adaptive")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

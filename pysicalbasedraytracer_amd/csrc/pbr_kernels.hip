@@ -674,6 +674,7 @@ __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
 #include "pbr_wavefront.h"
 #include "pbr_wavefront_path.h"
 #include "pbr_wavefront_volpath.h"
+#include "pbr_adaptive.h"
 
 // ---------------------------------------------------------------- introspection kernels
 __global__ void k_sampler_values(DeviceSampler smp, HaltonParams hp, int n, const int32_t* q, float* out) {
@@ -999,6 +1000,10 @@ struct pbr_hip_ctx {
     std::vector<FrameEv> frameEv;        // (pbr_hip_wait_frame)
     int batchFrames = 0;                 // frames of the last batch
     hipEvent_t evPass[kWfLanes] = {};    // sample passes rotating over the lanes: chunk c's last finish (pass_order)
+    // adaptive sampling (pbr_adaptive.h): the decision flags and block counts of a select or a run
+    // encoding, the words the host reads (active, runs, bad list), the two lists pbr_hip_render_adaptive
+    // alternates between, and a listed pass's tiles, dense accumulator and dense images
+    DevBuf dAdFlags, dAdBlock, dAdWords, dAdList[2], dRunTiles, dRunStart, dListAccum, dListRgb, dListRgba;
     // Whitted: per lane, a stream for the shadow rays and per-level events (shade done, shadow done)
     hipStream_t shadowStream[kWfLanes] = {};
     hipEvent_t evShade[kWfLanes][kWfMaxDepth + 2] = {}, evShadow[kWfLanes][kWfMaxDepth + 2] = {};
@@ -1289,6 +1294,10 @@ struct FrameSet {
     float* accum = nullptr;
     int first = 0, passSpp = 0;
     std::vector<const uint32_t*> sobolPass;   // wide Sobol indices: pass f's table (sobol_pass_table), else empty
+    // a pass over a list (pbr_hip_render_passes_list): the nList listed pixels only, as the nRuns tiles
+    // list_encode left in ctx->dRunTiles; accum, rgb[0], rgba[0] stay the frame's buffers
+    const int32_t* list = nullptr;
+    int nList = 0, nRuns = 0;
 };
 // Passes share `accum`: pass p+1's finish over a pixel range reads what pass p's finish over that
 // range wrote.  Passes of several chunks fork and join per pass, which orders them; passes that
@@ -2263,6 +2272,117 @@ int pbr_hip_upload_scene(pbr_hip_ctx* ctx, const pbr_scene_desc* desc) {
     return PBR_OK;
 }
 
+// The descriptor's tiles (none: the whole raster) on the device, in ctx->dTiles / dTileStart; *npx their
+// pixels.  Re-uploaded on change only.
+static int frame_tiles(pbr_hip_ctx* ctx, const pbr_render_desc* d, hipStream_t s, long long* npxOut, int* nTilesOut) {
+    std::vector<int32_t> tiles;
+    std::vector<long long> starts;
+    long long npx = 0;
+    if (d->n_tiles > 0) {
+        if (!d->tiles) return set_err(ctx, PBR_E_INVALID, "tiles == NULL");
+        for (int i = 0; i < d->n_tiles; ++i) {
+            const pbr_tile& t = d->tiles[i];
+            if (t.x0 < 0 || t.y0 < 0 || t.x1 > d->camera.width || t.y1 > d->camera.height || t.x1 <= t.x0 || t.y1 <= t.y0)
+                return set_err(ctx, PBR_E_INVALID, "tile outside the raster");
+            tiles.insert(tiles.end(), {t.x0, t.y0, t.x1, t.y1});
+            starts.push_back(npx);
+            npx += (long long)(t.x1 - t.x0) * (t.y1 - t.y0);
+        }
+    } else {
+        tiles = {0, 0, d->camera.width, d->camera.height};
+        starts.push_back(0);
+        npx = (long long)d->camera.width * d->camera.height;
+    }
+    // Device-output renders without host-side stats return without synchronising, so frames can
+    // queue back to back.  The context's queues are reused by every frame: a render on another
+    // stream first drains the previous one.
+    if (ctx->lastStream != s) {
+        if (int rc = drain(ctx)) return rc;
+    }
+    if (tiles != ctx->tilesHost || starts != ctx->startsHost) {
+        HIP_TRY(hipStreamSynchronize(s));   // an earlier async copy may still read the host copies
+        ctx->tilesHost = tiles;
+        ctx->startsHost = starts;
+        HIP_TRY(ctx->dTiles.upload(ctx->tilesHost, s));
+        HIP_TRY(ctx->dTileStart.upload(ctx->startsHost, s));
+    }
+    *npxOut = npx;
+    *nTilesOut = (int)starts.size();
+    return PBR_OK;
+}
+
+// ---- adaptive sampling (pbr_adaptive.h).  The words the host reads: ctx->dAdWords[0] the entries a
+// select left active, [1] the runs of the list last encoded, [2] set when that list was not ascending
+// pixels of the frame.
+static int adapt_scratch(pbr_hip_ctx* ctx, long long n) {
+    HIP_TRY(ctx->dAdFlags.ensure((size_t)n));
+    HIP_TRY(ctx->dAdBlock.ensure((size_t)((n + kAdaptBS - 1) / kAdaptBS) * sizeof(int)));
+    HIP_TRY(ctx->dAdWords.ensure(4 * sizeof(int)));
+    return PBR_OK;
+}
+// Queues the select over n entries (listIn == nullptr: pixels 0..n-1) at k samples done; the active
+// ones land in listOut in order, their number in dAdWords[0].
+static int adapt_select(pbr_hip_ctx* ctx, hipStream_t s, int nPixels, int k, float tolerance, float floor, const float* accum,
+                        const int32_t* listIn, int n, int32_t* listOut, float* errOut) {
+    if (int rc = adapt_scratch(ctx, n)) return rc;
+    int* words = (int*)ctx->dAdWords.p;
+    const int nBlocks = (n + kAdaptBS - 1) / kAdaptBS;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(words, 0, sizeof(int), s));
+        return PBR_OK;
+    }
+    const dim3 grid(nBlocks), blk(kAdaptBS);
+    hipLaunchKernelGGL(k_adapt_select, grid, blk, 0, s, accum, listIn, n, nPixels, k, tolerance, floor, (uint8_t*)ctx->dAdFlags.p,
+                       (int*)ctx->dAdBlock.p, errOut);
+    hipLaunchKernelGGL(k_adapt_scan, dim3(1), blk, 0, s, (int*)ctx->dAdBlock.p, nBlocks, (const int*)nullptr, words);
+    hipLaunchKernelGGL(k_adapt_compact, grid, blk, 0, s, listIn, n, (const uint8_t*)ctx->dAdFlags.p, (const int*)ctx->dAdBlock.p,
+                       listOut);
+    HIP_TRY(hipGetLastError());
+    return PBR_OK;
+}
+// Queues the run encoding of `list` against the frame's tiles (frame_tiles) into ctx->dRunTiles /
+// dRunStart; the run count lands in dAdWords[1].  nMax bounds the list's length; lengthOnDevice: the
+// length is dAdWords[0] (the select queued just before).
+static int list_encode(pbr_hip_ctx* ctx, hipStream_t s, const int32_t* list, int nMax, bool lengthOnDevice, long long framePixels,
+                       int frameTiles) {
+    if (int rc = adapt_scratch(ctx, nMax)) return rc;
+    HIP_TRY(ctx->dRunTiles.ensure((size_t)nMax * sizeof(int4)));
+    HIP_TRY(ctx->dRunStart.ensure((size_t)nMax * sizeof(long long)));
+    int* words = (int*)ctx->dAdWords.p;
+    HIP_TRY(hipMemsetAsync(words + 1, 0, 2 * sizeof(int), s));
+    if (nMax == 0) return PBR_OK;
+    AdaptFrame A;
+    A.tiles = (const int4*)ctx->dTiles.p;
+    A.tileStart = (const long long*)ctx->dTileStart.p;
+    A.nTiles = frameTiles;
+    A.nPixels = framePixels;
+    const int nBlocks = (nMax + kAdaptBS - 1) / kAdaptBS;
+    const dim3 grid(nBlocks), blk(kAdaptBS);
+    const int* nDev = lengthOnDevice ? words : nullptr;
+    hipLaunchKernelGGL(k_adapt_run_flags, grid, blk, 0, s, list, nMax, nDev, A, (uint8_t*)ctx->dAdFlags.p, (int*)ctx->dAdBlock.p,
+                       words + 2);
+    hipLaunchKernelGGL(k_adapt_scan, dim3(1), blk, 0, s, (int*)ctx->dAdBlock.p, nBlocks, nDev, words + 1);
+    hipLaunchKernelGGL(k_adapt_run_encode, grid, blk, 0, s, list, nMax, nDev, A, (const uint8_t*)ctx->dAdFlags.p,
+                       (const int*)ctx->dAdBlock.p, (int4*)ctx->dRunTiles.p, (long long*)ctx->dRunStart.p);
+    HIP_TRY(hipGetLastError());
+    return PBR_OK;
+}
+static int adapt_read_words(pbr_hip_ctx* ctx, hipStream_t s, int first, int count, int* out) {
+    HIP_TRY(hipMemcpyAsync(out, (const int*)ctx->dAdWords.p + first, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PBR_OK;
+}
+// The sampler's samplesPerPixel for d->spp (make_params: Sobol rounds up to a power of two).
+static long long sample_budget(const pbr_render_desc* d) {
+    long long spp = d->spp;
+    if (d->sampler == PBR_SAMPLER_SOBOL) {
+        long long p2 = 1;
+        while (p2 < spp) p2 <<= 1;
+        spp = p2;
+    }
+    return spp;
+}
+
 static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_out, uint8_t* rgba_out, pbr_render_stats* stats,
                        FrameSet F) {
     if (!ctx) return PBR_E_INVALID;
@@ -2315,41 +2435,35 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
     }
     const int spp = P.spp;
     // tiles
-    std::vector<int32_t> tiles;
-    std::vector<long long> starts;
     long long npx = 0;
-    if (d->n_tiles > 0) {
-        if (!d->tiles) return set_err(ctx, PBR_E_INVALID, "tiles == NULL");
-        for (int i = 0; i < d->n_tiles; ++i) {
-            const pbr_tile& t = d->tiles[i];
-            if (t.x0 < 0 || t.y0 < 0 || t.x1 > d->camera.width || t.y1 > d->camera.height || t.x1 <= t.x0 || t.y1 <= t.y0)
-                return set_err(ctx, PBR_E_INVALID, "tile outside the raster");
-            tiles.insert(tiles.end(), {t.x0, t.y0, t.x1, t.y1});
-            starts.push_back(npx);
-            npx += (long long)(t.x1 - t.x0) * (t.y1 - t.y0);
-        }
-    } else {
-        tiles = {0, 0, d->camera.width, d->camera.height};
-        starts.push_back(0);
-        npx = (long long)d->camera.width * d->camera.height;
-    }
-    // Device-output renders without host-side stats return without synchronising, so frames can
-    // queue back to back.  The context's queues are reused by every frame: a render on another
-    // stream first drains the previous one.
-    if (ctx->lastStream != s) {
-        if (int rc = drain(ctx)) return rc;
-    }
-    if (tiles != ctx->tilesHost || starts != ctx->startsHost) {
-        HIP_TRY(hipStreamSynchronize(s));   // an earlier async copy may still read the host copies
-        ctx->tilesHost = tiles;
-        ctx->startsHost = starts;
-        HIP_TRY(ctx->dTiles.upload(ctx->tilesHost, s));
-        HIP_TRY(ctx->dTileStart.upload(ctx->startsHost, s));
-    }
+    if (int rc = frame_tiles(ctx, d, s, &npx, &P.nTiles)) return rc;
     P.tiles = (const int4*)ctx->dTiles.p;
     P.tileStart = (const long long*)ctx->dTileStart.p;
-    P.nTiles = (int)starts.size();
     P.nPixels = npx;
+    // A pass over a list: the listed pixels' sums are gathered into a dense accumulator, and the pass
+    // renders the list's runs as tiles (list_encode) against it and dense images; list_scatter below
+    // takes the results to the frame's buffers.
+    float* frameRgb = nullptr;
+    uint8_t* frameRgba = nullptr;
+    float* denseRgb[1] = {nullptr};
+    uint8_t* denseRgba[1] = {nullptr};
+    if (F.list) {
+        if ((long long)F.nList > npx) return set_err(ctx, PBR_E_INVALID, "render_passes_list: more listed pixels than the tiles hold");
+        frameRgb = F.rgb ? F.rgb[0] : nullptr;
+        frameRgba = F.rgba ? F.rgba[0] : nullptr;
+        HIP_TRY(ctx->dListAccum.ensure((size_t)F.nList * 6 * sizeof(float)));
+        if (frameRgb) { HIP_TRY(ctx->dListRgb.ensure((size_t)F.nList * 12)); denseRgb[0] = (float*)ctx->dListRgb.p; }
+        if (frameRgba) { HIP_TRY(ctx->dListRgba.ensure((size_t)F.nList * 4)); denseRgba[0] = (uint8_t*)ctx->dListRgba.p; }
+        hipLaunchKernelGGL(k_adapt_gather, dim3((F.nList + kAdaptBS - 1) / kAdaptBS), dim3(kAdaptBS), 0, s, F.list, F.nList,
+                           F.accum, (float*)ctx->dListAccum.p);
+        F.rgb = denseRgb;
+        F.rgba = denseRgba;
+        P.accum = (float*)ctx->dListAccum.p;
+        P.tiles = (const int4*)ctx->dRunTiles.p;
+        P.tileStart = (const long long*)ctx->dRunStart.p;
+        P.nTiles = F.nRuns;
+        P.nPixels = npx = F.nList;
+    }
     // outputs
     if (d->outputs_on_device) {
         P.rgbOut = rgb_out;
@@ -2414,6 +2528,12 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
             }
         }
 #undef PBR_LAUNCH
+        if (F.list) {   // (every lane is joined back into `s` by now; the pass's event moves behind the scatter)
+            hipLaunchKernelGGL(k_adapt_scatter, dim3((F.nList + kAdaptBS - 1) / kAdaptBS), dim3(kAdaptBS), 0, s, F.list, F.nList,
+                               (const float*)ctx->dListAccum.p, (const float*)denseRgb[0], (const uint32_t*)denseRgba[0],
+                               F.accum, frameRgb, (uint32_t*)frameRgba);
+            if (int rc = wf_frame_done(ctx, s, 0, 0u)) return rc;
+        }
         HIP_TRY(hipGetLastError());
     }
     if (F.batch) ctx->batchFrames = F.n;
@@ -2489,6 +2609,142 @@ int pbr_hip_render_passes(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_
     F.first = first_sample;
     F.passSpp = samples_per_pass;
     return render_impl(ctx, d, nullptr, nullptr, nullptr, F);
+}
+
+int pbr_hip_adaptive_select(pbr_hip_ctx* ctx, int64_t n_pixels, int samples_done, float tolerance, float floor, const float* accum,
+                            const int32_t* list_in, int n_in, int32_t* list_out, int* n_out, float* err_out) {
+    if (!ctx) return PBR_E_INVALID;
+    if (samples_done < 2) return set_err(ctx, PBR_E_INVALID, "adaptive_select: samples_done must be >= 2");
+    if (n_pixels < 1 || n_pixels >= (1ll << 31)) return set_err(ctx, PBR_E_INVALID, "adaptive_select: n_pixels must be in [1, 2^31)");
+    if (!(tolerance >= 0.f) || !(floor >= 0.f)) return set_err(ctx, PBR_E_INVALID, "adaptive_select: tolerance and floor must be >= 0");
+    if (!accum || !list_out || !n_out) return set_err(ctx, PBR_E_INVALID, "adaptive_select: accum, list_out and n_out are required");
+    if (list_in && (n_in < 0 || (int64_t)n_in > n_pixels)) return set_err(ctx, PBR_E_INVALID, "adaptive_select: n_in must be in [0, n_pixels]");
+    if (list_in && list_in == list_out) return set_err(ctx, PBR_E_INVALID, "adaptive_select: list_out must not be list_in");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = drain(ctx)) return rc;   // (the sums may come from a render still in flight)
+    const int n = list_in ? n_in : (int)n_pixels;
+    if (int rc = adapt_select(ctx, ctx->stream, (int)n_pixels, samples_done, tolerance, floor, accum, list_in, n, list_out, err_out))
+        return rc;
+    return adapt_read_words(ctx, ctx->stream, 0, 1, n_out);
+}
+
+// What the listed-pass entry points share with pbr_hip_render_passes, checked before anything is queued.
+static int list_pass_check(pbr_hip_ctx* ctx, const pbr_render_desc* d, const char* who, long long* budget) {
+    const std::string w(who);
+    if (!d) return set_err(ctx, PBR_E_INVALID, w + ": null render desc");
+    if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
+    if (d->sampler == PBR_SAMPLER_TABLE) return set_err(ctx, PBR_E_UNSUPPORTED, w + ": no passes over a sample table");
+    if (!d->outputs_on_device || d->collect_stats) return set_err(ctx, PBR_E_INVALID, w + ": device outputs, no stats");
+    if (d->spp < 1) return set_err(ctx, PBR_E_INVALID, "spp must be positive");
+    *budget = sample_budget(d);
+    return PBR_OK;
+}
+static FrameSet list_frame_set(int first, int samples, const int32_t* list, int nList, int nRuns, float* accum, float* const* rgb,
+                               uint8_t* const* rgba) {
+    FrameSet F;
+    F.n = 1;
+    F.rgb = rgb;
+    F.rgba = rgba;
+    F.batch = true;
+    F.accum = accum;
+    F.first = first;
+    F.passSpp = samples;
+    F.list = list;
+    F.nList = nList;
+    F.nRuns = nRuns;
+    return F;
+}
+
+int pbr_hip_render_passes_list(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sample, int samples, const int32_t* list,
+                               int n_list, float* accum, float* rgb_out, uint8_t* rgba_out) {
+    if (!ctx) return PBR_E_INVALID;
+    long long budget = 0;
+    if (int rc = list_pass_check(ctx, d, "render_passes_list", &budget)) return rc;
+    if (!accum) return set_err(ctx, PBR_E_INVALID, "render_passes_list: accum must be a device buffer of 6 floats per pixel");
+    if (samples < 1) return set_err(ctx, PBR_E_INVALID, "render_passes_list: samples must be >= 1");
+    if (first_sample < 0) return set_err(ctx, PBR_E_INVALID, "render_passes_list: first_sample must be >= 0");
+    if ((long long)first_sample + samples > budget)
+        return set_err(ctx, PBR_E_INVALID, "render_passes_list: samples [" + std::to_string(first_sample) + ", " +
+                       std::to_string((long long)first_sample + samples) + ") run past the budget of " + std::to_string(budget) +
+                       " samples per pixel");
+    if (n_list < 0 || (n_list > 0 && !list)) return set_err(ctx, PBR_E_INVALID, "render_passes_list: n_list >= 0 and a list");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
+    long long npx = 0;
+    int nTiles = 0;
+    if (int rc = frame_tiles(ctx, d, s, &npx, &nTiles)) return rc;
+    if (npx >= (1ll << 31)) return set_err(ctx, PBR_E_UNSUPPORTED, "render_passes_list: pixel indices beyond int32");
+    if ((long long)n_list > npx) return set_err(ctx, PBR_E_INVALID, "render_passes_list: more listed pixels than the tiles hold");
+    if (n_list == 0) {   // nothing to render: an empty batch of one finished pass
+        ctx->batchFrames = 0;
+        if (int rc = wf_frame_done(ctx, s, 0, 0u)) return rc;
+        ctx->batchFrames = 1;
+        return PBR_OK;
+    }
+    if (int rc = list_encode(ctx, s, list, n_list, false, npx, nTiles)) return rc;
+    int w[2] = {0, 0};   // runs, bad list
+    if (int rc = adapt_read_words(ctx, s, 1, 2, w)) return rc;
+    if (w[1]) return set_err(ctx, PBR_E_INVALID, "render_passes_list: the list must hold ascending packed pixel indices of the tiles");
+    float* rgb[1] = {rgb_out};
+    uint8_t* rgba[1] = {rgba_out};
+    return render_impl(ctx, d, nullptr, nullptr, nullptr, list_frame_set(first_sample, samples, list, n_list, w[0], accum, rgb, rgba));
+}
+
+int pbr_hip_render_adaptive(pbr_hip_ctx* ctx, const pbr_render_desc* d, const pbr_adaptive* a, float* accum, int32_t* counts,
+                            float* rgb_out, uint8_t* rgba_out, pbr_adaptive_result* result) {
+    if (!ctx) return PBR_E_INVALID;
+    long long budget = 0;
+    if (int rc = list_pass_check(ctx, d, "render_adaptive", &budget)) return rc;
+    if (!a || !accum || !counts) return set_err(ctx, PBR_E_INVALID, "render_adaptive: parameters, accum and counts are required");
+    if (a->min_samples < 2 || a->min_samples > budget)
+        return set_err(ctx, PBR_E_INVALID, "render_adaptive: min_samples must be in [2, " + std::to_string(budget) + "] (the budget)");
+    if (a->samples_per_round < 1) return set_err(ctx, PBR_E_INVALID, "render_adaptive: samples_per_round must be >= 1");
+    if (!(a->tolerance >= 0.f) || !(a->floor >= 0.f)) return set_err(ctx, PBR_E_INVALID, "render_adaptive: tolerance and floor must be >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
+    long long npx = 0;
+    int nTiles = 0;
+    if (int rc = frame_tiles(ctx, d, s, &npx, &nTiles)) return rc;
+    if (npx >= (1ll << 31)) return set_err(ctx, PBR_E_UNSUPPORTED, "render_adaptive: pixel indices beyond int32");
+    float* rgb[1] = {rgb_out};
+    uint8_t* rgba[1] = {rgba_out};
+    // 1. every pixel takes min_samples: a plain full-frame pass
+    int k = a->min_samples;
+    if (int rc = pbr_hip_render_passes(ctx, d, 0, k, 1, accum, rgb, rgba)) return rc;
+    const dim3 blk(kAdaptBS);
+    hipLaunchKernelGGL(k_adapt_counts, dim3((unsigned)((npx + kAdaptBS - 1) / kAdaptBS)), blk, 0, s, (const int32_t*)nullptr, (int)npx,
+                       counts, k);
+    HIP_TRY(ctx->dAdList[0].ensure((size_t)npx * sizeof(int32_t)));
+    pbr_adaptive_result R = {1, k, npx * k, 0};
+    // 2. rounds: the select over the current list and the run encoding of what it leaves are queued
+    // together, and one 8-byte copy (active pixels, runs) tells the host whether and what to render
+    const int32_t* list = nullptr;
+    int n = (int)npx, cur = 0;
+    for (;;) {
+        int32_t* next = (int32_t*)ctx->dAdList[cur].p;
+        if (int rc = adapt_select(ctx, s, (int)npx, k, a->tolerance, a->floor, accum, list, n, next, nullptr)) return rc;
+        const bool more = k < budget;
+        if (more) { if (int rc = list_encode(ctx, s, next, n, true, npx, nTiles)) return rc; }
+        int w[2] = {0, 0};
+        if (int rc = adapt_read_words(ctx, s, 0, 2, w)) return rc;
+        R.active_at_end = w[0];
+        if (!more || w[0] == 0) break;
+        const int step = (int)std::min<long long>(a->samples_per_round, budget - k);
+        if (int rc = render_impl(ctx, d, nullptr, nullptr, nullptr, list_frame_set(k, step, next, w[0], w[1], accum, rgb, rgba))) return rc;
+        k += step;
+        hipLaunchKernelGGL(k_adapt_counts, dim3((w[0] + kAdaptBS - 1) / kAdaptBS), blk, 0, s, (const int32_t*)next, w[0], counts, k);
+        list = next;
+        n = w[0];
+        cur ^= 1;
+        HIP_TRY(ctx->dAdList[cur].ensure((size_t)n * sizeof(int32_t)));
+        ++R.rounds;
+        R.max_samples_done = k;
+        R.samples += (int64_t)n * step;
+    }
+    if (int rc = drain(ctx)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (result) *result = R;
+    return PBR_OK;
 }
 
 int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f) {

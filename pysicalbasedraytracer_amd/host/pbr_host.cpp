@@ -1564,20 +1564,40 @@ struct SamplerIntegrator::Progressive {
 };
 
 void SamplerIntegrator::RenderSamples(const Scene& scene, int firstSample, int nSamples) {
-    if (!devices.empty()) throw std::invalid_argument("RenderSamples: one device (SetDevice), not SetDevices");
-    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
-    if (!cam) throw std::invalid_argument("RenderSamples: only PerspectiveCamera is on the GPU path");
-    check_sampler(*sampler, *cam, "RenderSamples");
-    if (sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
-        throw std::invalid_argument("RenderSamples: a custom sampler's values go to the device as a whole frame's table; "
-                                    "sample passes need HaltonSampler or SobolSampler");
     if (firstSample < 0 || nSamples < 1) throw std::invalid_argument("RenderSamples: firstSample >= 0 and nSamples >= 1");
+    RenderPass(scene, "RenderSamples", firstSample, nSamples, nullptr);
+}
+
+std::vector<int> SamplerIntegrator::RenderAdaptive(const Scene& scene, int minSamples, int samplesPerRound, float tolerance,
+                                                   float floor) {
+    const int budget = (int)sampler->samplesPerPixel;   // (SobolSampler has rounded it up already)
+    if (minSamples < 2 || minSamples > budget)
+        throw std::invalid_argument("RenderAdaptive: minSamples " + std::to_string(minSamples) + " outside [2, " +
+                                    std::to_string(budget) + "] (the sampler's samplesPerPixel)");
+    if (samplesPerRound < 1) throw std::invalid_argument("RenderAdaptive: samplesPerRound must be >= 1");
+    if (!(tolerance >= 0.f) || !(floor >= 0.f)) throw std::invalid_argument("RenderAdaptive: tolerance and floor must be >= 0");
+    const pbr_adaptive a = {minSamples, samplesPerRound, tolerance, floor};
+    return RenderPass(scene, "RenderAdaptive", 0, 0, &a);
+}
+
+// One pass of RenderSamples, or (adaptive != nullptr) a whole adaptive render from sample 0; returns
+// the adaptive render's per-pixel sample counts in packed tile order.
+std::vector<int> SamplerIntegrator::RenderPass(const Scene& scene, const char* whoName, int firstSample, int nSamples,
+                                               const pbr_adaptive* adaptive) {
+    const std::string who(whoName);
+    if (!devices.empty()) throw std::invalid_argument(who + ": one device (SetDevice), not SetDevices");
+    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
+    if (!cam) throw std::invalid_argument(who + ": only PerspectiveCamera is on the GPU path");
+    check_sampler(*sampler, *cam, whoName);
+    if (sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
+        throw std::invalid_argument(who + ": a custom sampler's values go to the device as a whole frame's table; "
+                                    "sample passes need HaltonSampler or SobolSampler");
     if (firstSample != 0 && (!prog || firstSample != samplesDone))
-        throw std::invalid_argument("RenderSamples: firstSample " + std::to_string(firstSample) + " does not continue the " +
+        throw std::invalid_argument(who + ": firstSample " + std::to_string(firstSample) + " does not continue the " +
                                     std::to_string(prog ? samplesDone : 0) + " samples done");
     const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;   // the reference reads pMax only
     if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
-        throw std::invalid_argument("RenderSamples: pixelBounds outside the camera raster");
+        throw std::invalid_argument(who + ": pixelBounds outside the camera raster");
     ensure_scene(scene);
     auto flat = FlattenScene(scene, cam->medium);   // for the camera medium's index
     pbr_render_desc rd;
@@ -1603,7 +1623,7 @@ void SamplerIntegrator::RenderSamples(const Scene& scene, int firstSample, int n
     for (const pbr_tile& t : tl) npx += (size_t)(t.x1 - t.x0) * (t.y1 - t.y0);
     hip_check(hipSetDevice(device), "hipSetDevice");
     if (!prog || prog->npx != npx || prog->device != device) {
-        if (firstSample != 0) throw std::invalid_argument("RenderSamples: the tiles changed since the last call");
+        if (firstSample != 0) throw std::invalid_argument(who + ": the tiles changed since the last call");
         prog = std::make_shared<Progressive>();
         prog->device = device;
         prog->npx = npx;
@@ -1614,16 +1634,32 @@ void SamplerIntegrator::RenderSamples(const Scene& scene, int firstSample, int n
     auto t0 = std::chrono::steady_clock::now();
     float* rgbOut[1] = {prog->rgb};
     uint8_t* rgbaOut[1] = {prog->rgba};
-    check(ctx, pbr_hip_render_passes(ctx, &rd, firstSample, nSamples, 1, prog->accum, rgbOut, rgbaOut), "pbr_hip_render_passes");
-    check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
-    samplesDone = firstSample + nSamples;
+    std::vector<int> counts;
+    uint64_t samplesTaken = (uint64_t)npx * (uint64_t)nSamples;
+    if (adaptive) {
+        int32_t* dCounts = nullptr;
+        hip_check(hipMalloc((void**)&dCounts, std::max<size_t>(1, npx) * sizeof(int32_t)), "hipMalloc");
+        pbr_adaptive_result res;
+        const int rc = pbr_hip_render_adaptive(ctx, &rd, adaptive, prog->accum, dCounts, prog->rgb, prog->rgba, &res);
+        counts.resize(npx);
+        const hipError_t e = rc == PBR_OK ? hipMemcpy(counts.data(), dCounts, npx * sizeof(int32_t), hipMemcpyDeviceToHost) : hipSuccess;
+        (void)hipFree(dCounts);
+        check(ctx, rc, "pbr_hip_render_adaptive");
+        hip_check(e, "hipMemcpy");
+        samplesDone = 0;   // (the pixels' counts differ: no image a RenderSamples pass could continue)
+        samplesTaken = (uint64_t)res.samples;
+    } else {
+        check(ctx, pbr_hip_render_passes(ctx, &rd, firstSample, nSamples, 1, prog->accum, rgbOut, rgbaOut), "pbr_hip_render_passes");
+        check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
+        samplesDone = firstSample + nSamples;
+    }
     std::vector<float> rgb(npx * 3);
     std::vector<uint8_t> rgba(npx * 4);
     hip_check(hipMemcpy(rgb.data(), prog->rgb, rgb.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
     hip_check(hipMemcpy(rgba.data(), prog->rgba, rgba.size(), hipMemcpyDeviceToHost), "hipMemcpy");
     if (m_FrameBuffer) {
         if (m_FrameBuffer->width != W || m_FrameBuffer->height != H || m_FrameBuffer->channals < 3)
-            throw std::invalid_argument("RenderSamples: FrameBuffer not initialised to the pixel bounds");
+            throw std::invalid_argument(who + ": FrameBuffer not initialised to the pixel bounds");
         size_t k = 0;
         for (const pbr_tile& t : tl)
             for (int y = t.y0; y < t.y1; ++y)
@@ -1635,7 +1671,8 @@ void SamplerIntegrator::RenderSamples(const Scene& scene, int firstSample, int n
     }
     stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     stats.kernel_ms = 0;   // (passes are enqueued without event timing)
-    stats.samples = (uint64_t)npx * (uint64_t)nSamples;
+    stats.samples = samplesTaken;
+    return counts;
 }
 
 struct SamplerIntegrator::MultiGPU {
