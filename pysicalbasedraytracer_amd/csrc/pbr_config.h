@@ -21,7 +21,8 @@
 #endif
 #endif
 // PBR_DIAG_SHADE (diagnostic builds only, results NOT the reference's): bits that stub parts of the
-// Path shade to price them (tools/r5_shade_probe.py).
+// shade to price them (tools/shade_probe.py): 1 the Path light sample's f and pdf, 2 and 4 the
+// estimate's BSDF sample and its Pdf_Li (shared by Path and VolPath), 8 the sampler.
 #ifndef PBR_DIAG_SHADE
 #define PBR_DIAG_SHADE 0
 #endif

@@ -206,7 +206,11 @@ PBR_HELPER void sphere_si(const SphereRec& s, const Ray& r, float t, Isect* si) 
     si->n = n;
     si->sn = n;
     si->dpdu = du;
-    si->u = si->v = 0.f;   // image textures are refused on spheres at upload
+    // (image textures are refused on spheres at upload.  u, then v, as triangle_si ends: with v
+    // first, the two functions' last stores were merged into one store through a pointer select
+    // inside hit_isect, which kept two Isect fields in scratch)
+    si->u = 0.f;
+    si->v = 0.f;
 }
 
 __device__ __forceinline__ bool prim_hit(const DeviceScene& S, int slot, const Ray& r, float* t, float* b0, float* b1, float* b2) {
@@ -841,19 +845,30 @@ __device__ bool traverse(const DeviceScene& S, Ray& r, HitRec* h, Counters* c) {
     return found;
 }
 
+// The SurfaceInteraction of a closest hit (sphere or triangle), for the ray whose tMax the walk
+// left at the hit.  The medium interface is not set: set_interface, or none (Path, Whitted).
+__device__ __forceinline__ void hit_isect(const DeviceScene& S, const HitRec& h, const Ray& r, Isect* si) {
+    const int flags = __float_as_int(S.triVerts[3 * (size_t)h.slot].w);
+    if (flags & PRIM_SPHERE) sphere_si(S.spheres[__float_as_int(S.triVerts[3 * (size_t)h.slot].x)], r, r.tMax, si);
+    else triangle_si(S, h.slot, r, h.b0, h.b1, h.b2, flags, si);
+    si->slot = h.slot;
+}
+
+// Scene::Intersect's medium interface on a hit (Primitive.cpp:30-34)
+__device__ __forceinline__ void set_interface(const DeviceScene& S, Isect* si, int rayMedium) {
+    int4 info = S.primInfo[si->slot];
+    int mi = (int)(short)(info.w & 0xffff), mo = (int)(short)((info.w >> 16) & 0xffff);
+    if (mi != mo) { si->medIn = mi; si->medOut = mo; }
+    else { si->medIn = rayMedium; si->medOut = rayMedium; }
+}
+
 // Scene::Intersect + SurfaceInteraction construction for the surviving primitive.
 template <bool STATS>
 __device__ bool intersect(const DeviceScene& S, Ray& r, Isect* si, Counters* c) {
     HitRec h;
     if (!traverse<false, STATS>(S, r, &h, c)) return false;
-    int flags = __float_as_int(S.triVerts[3 * (size_t)h.slot].w);
-    if (flags & PRIM_SPHERE) sphere_si(S.spheres[__float_as_int(S.triVerts[3 * (size_t)h.slot].x)], r, r.tMax, si);
-    else triangle_si(S, h.slot, r, h.b0, h.b1, h.b2, flags, si);
-    si->slot = h.slot;
-    int4 info = S.primInfo[h.slot];
-    int mi = (int)(short)(info.w & 0xffff), mo = (int)(short)((info.w >> 16) & 0xffff);
-    if (mi != mo) { si->medIn = mi; si->medOut = mo; }     // Primitive.cpp:30-34
-    else { si->medIn = r.medium; si->medOut = r.medium; }
+    hit_isect(S, h, r, si);
+    set_interface(S, si, r.medium);
     return true;
 }
 

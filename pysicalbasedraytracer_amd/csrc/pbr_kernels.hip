@@ -758,9 +758,9 @@ __global__ void k_query(DeviceScene S, const int32_t* primIds, int n, const floa
     if (hit && !any) {
         const int flags = __float_as_int(S.triVerts[3 * (size_t)h.slot].w);
         Isect si;
+        hit_isect(S, h, r, &si);
         if (flags & PRIM_SPHERE) {
             const SphereRec& sph = S.spheres[__float_as_int(S.triVerts[3 * (size_t)h.slot].x)];
-            sphere_si(sph, r, r.tMax, &si);
             // pbrt-v3 Sphere::Intersect's (u, v): phi / phiMax, (theta - thetaMin) / (thetaMax - thetaMin)
             f3 ob = xf_point(sph.w2o, r.o), db = xf_vector(sph.w2o, r.d);
             f3 ph = ob + db * r.tMax;
@@ -772,7 +772,6 @@ __global__ void k_query(DeviceScene S, const int32_t* primIds, int n, const floa
             o.uv[0] = phi / (2 * kPi);
             o.uv[1] = (theta - kPi) / (0.f - kPi);
         } else {
-            triangle_si(S, h.slot, r, h.b0, h.b1, h.b2, flags, &si);
             float u0x = 0, u0y = 0, u1x = 1, u1y = 0, u2x = 1, u2y = 1;   // Triangle::GetUVs default
             if (flags & PRIM_HAS_UV) {
                 const float2* uv = S.triUV + 3 * (size_t)h.slot;

@@ -526,6 +526,18 @@ constexpr int kMatteMirrorLobes = (1 << L_LAMBERT) | (1 << L_SPEC_R);
 // them with dependent loads).
 constexpr int kLdsMats = 32;
 __shared__ MatTemplate s_mats[kLdsMats];
+// The templates a shade kernel reads: the scene's, or the workgroup's LDS copy of them (every thread
+// calls it; the kernel's next barrier publishes the copy).
+template <bool MATS_LDS>
+__device__ __forceinline__ const MatTemplate* stage_mats(const DeviceScene& S) {
+    if constexpr (!MATS_LDS) return S.materials;
+    constexpr int words = (int)(sizeof(MatTemplate) / 4);
+    const int n = 2 * S.nMaterials * words;
+    const uint32_t* src = (const uint32_t*)S.materials;
+    uint32_t* dst = (uint32_t*)s_mats;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
+    return s_mats;
+}
 
 // Waves per SIMD of the Whitted shade kernel for the simple lobe set (C2).  Measured (C2 ms):
 // round 1 4: 19.97, 3: 20.16, 5: 20.11; round 3 4: 17.91-18.02, 3: 18.64, 5: 18.55.
@@ -604,15 +616,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0) {
     const KParams& P = W.P;
     const DeviceScene& S = P.S;
     stage_halton_lds(P.smp);
-    const MatTemplate* mats = S.materials;
-    if constexpr (MATS_LDS) {
-        constexpr int words = (int)(sizeof(MatTemplate) / 4);
-        const int n = 2 * S.nMaterials * words;
-        const uint32_t* src = (const uint32_t*)S.materials;
-        uint32_t* dst = (uint32_t*)s_mats;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-        mats = s_mats;
-    }
+    const MatTemplate* mats = stage_mats<MATS_LDS>(S);
     __shared__ int s_push[2];   // shadow, next
     if (threadIdx.x < 2) s_push[threadIdx.x] = 0;
     __syncthreads();
@@ -666,10 +670,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0) {
                     }
                 }
                 Isect isect;
-                int flags = __float_as_int(S.triVerts[3 * (size_t)slot].w);
-                if (flags & PRIM_SPHERE) sphere_si(S.spheres[__float_as_int(S.triVerts[3 * (size_t)slot].x)], ray, ray.tMax, &isect);
-                else triangle_si(S, slot, ray, hr.y, hr.z, hr.w, flags, &isect);
-                isect.slot = slot;
+                hit_isect(S, HitRec{slot, hr.y, hr.z, hr.w}, ray, &isect);
                 isect.medIn = isect.medOut = -1;
                 BSDF bsdf;
                 MatTemplate texLocal;   // a textured material's per-hit lobes (make_bsdf)
@@ -843,15 +844,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade_ml(WfParams W, int level0
     const KParams& P = W.P;
     const DeviceScene& S = P.S;
     stage_halton_lds(P.smp);
-    const MatTemplate* mats = S.materials;
-    if constexpr (MATS_LDS) {
-        constexpr int words = (int)(sizeof(MatTemplate) / 4);
-        const int n = 2 * S.nMaterials * words;
-        const uint32_t* src = (const uint32_t*)S.materials;
-        uint32_t* dst = (uint32_t*)s_mats;
-        for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-        mats = s_mats;
-    }
+    const MatTemplate* mats = stage_mats<MATS_LDS>(S);
     __shared__ int s_push[2];   // shadow, next
     if (threadIdx.x < 2) s_push[threadIdx.x] = 0;
     __syncthreads();
@@ -888,10 +881,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade_ml(WfParams W, int level0
                 for (int k = 0; k < nL; ++k) W.recV[((size_t)depth * nL + k) * W.cap + id] = 0;
                 W.depthOf[id] = depth;
             } else {
-                int flags = __float_as_int(S.triVerts[3 * (size_t)slot].w);
-                if (flags & PRIM_SPHERE) sphere_si(S.spheres[__float_as_int(S.triVerts[3 * (size_t)slot].x)], ray, ray.tMax, &isect);
-                else triangle_si(S, slot, ray, hr.y, hr.z, hr.w, flags, &isect);
-                isect.slot = slot;
+                hit_isect(S, HitRec{slot, hr.y, hr.z, hr.w}, ray, &isect);
                 isect.medIn = isect.medOut = -1;
                 if (!make_bsdf<(LOBES & kTexturedLobes) != 0>(S, mats, isect, false, &bsdf, &texLocal)) {
                     cont = spawn_ray(isect, ray.d);        // Li(isect.SpawnRay(ray.d), depth)

@@ -397,7 +397,7 @@ SCHEDULES.update({name: kw for name, (kw, _) in FOUR_LANES.items()})
 
 
 def wavefront_equals_megakernel(hip, rd, sched):
-    """The frame under SCHEDULES[sched] and under the megakernel: the same bits.  The four-lane
+    """The frame under SCHEDULES[sched] and under the megakernel (returned): the same bits.  The four-lane
     schedules also render asynchronously into NaN-filled device buffers, on a caller's stream (lane 0
     then runs on the context's stream) and on the context's own, in the regime they are named for."""
     import torch
@@ -408,7 +408,7 @@ def wavefront_equals_megakernel(hip, rd, sched):
     assert np.array_equal(wf.view(np.uint32), mk.view(np.uint32)), float(np.abs(wf - mk).max())
     assert np.array_equal(wf8, mk8)
     if sched not in FOUR_LANES:
-        return
+        return mk
     dev = torch.device("cuda", 0)
     npx = HipRenderer.n_pixels(rd)
     for stream in (torch.cuda.Stream(dev), None):
@@ -421,15 +421,80 @@ def wavefront_equals_megakernel(hip, rd, sched):
         torch.cuda.synchronize()
         assert np.array_equal(rgb.cpu().numpy().view(np.uint32), mk.reshape(npx, 3).view(np.uint32)), stream
         assert np.array_equal(rgba.cpu().numpy(), mk8.reshape(npx, 4)), stream
+    return mk
 
 
-@pytest.mark.parametrize("sched", sorted(SCHEDULES))
-@pytest.mark.parametrize("config", ["c3", "c4", "c3_power"])
+# Scenes that send the Path / VolPath shade down the branches of its launch ladder
+# (render_wavefront_path) that the configs do not reach; each runs under the default schedule only.
+#   many_simple   more than 16 materials (the templates are not staged in LDS), simple lobes only
+#   many_mixed    the same with a mirror next to a rough lobe: neither the simple nor the microfacet set
+#   few_mixed     that lobe mix with few materials (all lobes, templates in LDS)
+#   micro_sobol   microfacet materials under Sobol (the microfacet set without the sampler
+#                 specialisation, and not classed)
+#   glass_sobol   VolPath: matte + specular glass under Sobol (simple lobes)
+#   c5_point      VolPath: C5's shape with a point light, so medium events estimate a delta light
+PATH_LADDER = ["many_simple", "many_mixed", "few_mixed", "micro_sobol"]
+VOL_LADDER = PATH_LADDER + ["glass_sobol", "c5_point"]
+
+
+def ladder_scene(case, vol):
+    """48x27 at 4 spp, depth 5: a body (a dragon stand-in; VolPath: filled with C5's medium) on a
+    floor under C3's area light."""
+    s = scenes.Scene()
+    white = s.matte((0.8, 0.8, 0.8))
+    if case.startswith("many"):
+        for k in range(16):
+            s.matte((0.1 + 0.05 * k, 0.5, 0.9 - 0.05 * k))
+    floor, sampler = white, capi.SAMPLER_HALTON
+    if case == "many_simple":
+        body = s.glass(urough=0.0, vrough=0.0) if vol else s.matte((0.0, 1.0, 0.0))
+    elif case in ("many_mixed", "few_mixed"):
+        floor = s.mirror((0.9, 0.9, 0.9))
+        body = s.glass() if vol else s.metal()
+    elif case == "micro_sobol":
+        body, sampler = (s.glass() if vol else s.plastic()), capi.SAMPLER_SOBOL
+    elif case == "glass_sobol":
+        body, sampler = s.glass(urough=0.0, vrough=0.0), capi.SAMPLER_SOBOL
+    else:
+        assert case == "c5_point"
+        body = s.glass()
+    P, I, _ = small_dragon(40)
+    med = s.homogeneous_medium(0.5, 4.4, -0.5) if vol else -1
+    s.mesh(P, I, body, medium_inside=med, medium_outside=-1)
+    Pf, If = scenes.quad(-1.12, 6.0)
+    s.mesh(Pf, If, floor)
+    Pl, Il = scenes.quad(2.45, 1.4, flip=True)
+    s.area_light_mesh(Pl, Il, (5.0, 5.0, 5.0), white, n_samples=5)
+    if case == "c5_point":
+        s.point_light((1.0, 2.0, 1.5), (6.0, 5.0, 4.0))
+    cam = scenes.camera(48, 27, (0.0, 0.55, 2.6), (0.0, -0.25, 0.0))
+    integrator = capi.INTEGRATOR_VOLPATH if vol else capi.INTEGRATOR_PATH
+    return s, scenes.render_desc(cam, integrator, 4, 5, rr_threshold=1.0 if vol else 0.8, sampler=sampler)
+
+
+def ladder_case_equals_megakernel(hip, case, vol):
+    s, rd = ladder_scene(case, vol)
+    hip.upload(s)
+    mk = wavefront_equals_megakernel(hip, rd, "one_chunk")
+    assert np.any(mk != 0)
+    hip.set_profiling(2)
+    hip.render(rd)
+    prof = hip.get_profile()
+    hip.set_profiling(0)
+    if vol:   # both strategies of the light estimate ran
+        assert prof["k_wfv_tr"]["units"] > 0 and prof["k_wfp_probe"]["units"] > 0
+
+
+@pytest.mark.parametrize("config,sched",
+                         [pytest.param(c, s, id=f"{c}-{s}") for c in ["c3", "c4", "c3_power"] for s in sorted(SCHEDULES)]
+                         + [pytest.param(c, "one_chunk", id=c) for c in PATH_LADDER])
 def test_wavefront_path_equals_megakernel(hip, config, sched):
     """The wavefront Path schedule (shade / shadow / probe / resolve / extend) and the recursive
     megakernel produce identical bits: matte + area light with Sobol (C3), glass/metal/plastic
     with all lobe kinds (C4), and the power light distribution — as one chunk and as many chunks
-    over two or three lanes."""
+    over two or three lanes; and the scenes of PATH_LADDER."""
+    if config in PATH_LADDER:
+        return ladder_case_equals_megakernel(hip, config, vol=False)
     if config == "c4":
         s, rd = scenes.config_c4(96, 54, 8, mesh=small_dragon(40))
     else:
@@ -441,11 +506,14 @@ def test_wavefront_path_equals_megakernel(hip, config, sched):
     wavefront_equals_megakernel(hip, rd, sched)
 
 
-@pytest.mark.parametrize("sched", sorted(SCHEDULES))
-def test_wavefront_volpath_equals_megakernel(hip, sched):
+@pytest.mark.parametrize("config,sched", [pytest.param("c5", s, id=s) for s in sorted(SCHEDULES)]
+                         + [pytest.param(c, "one_chunk", id=c) for c in VOL_LADDER])
+def test_wavefront_volpath_equals_megakernel(hip, config, sched):
     """The wavefront VolPath schedule (medium sampling, HG phase, transmittance walks through the
     glass dragon's medium interface) matches the megakernel bit for bit (C5 shape), as one chunk
-    and as many chunks over two or three lanes."""
+    and as many chunks over two or three lanes; and the scenes of VOL_LADDER."""
+    if config in VOL_LADDER:
+        return ladder_case_equals_megakernel(hip, config, vol=True)
     s, rd = scenes.config_c5(80, 45, 8, mesh=small_dragon(40))
     hip.upload(s)
     wavefront_equals_megakernel(hip, rd, sched)
