@@ -736,6 +736,15 @@ class Integrator {
     virtual void Render(const Scene& scene, double& timeConsume) = 0;
     float IntegratorRenderTime = 0;
 };
+// SamplerIntegrator::RenderFeatures' result: per pixel of the pixel bounds, row by row in raster order
+// (row 0 is the top of the image; not flipped as the FrameBuffer is), over the samples done so far.
+struct FeatureBuffers {
+    int width = 0, height = 0;
+    std::vector<float> albedo;     // 3 per pixel: the mean albedo of the first surface the camera samples see
+    std::vector<float> normal;     // 3 per pixel: their mean world-space shading normal (not renormalised)
+    std::vector<float> depth;      // 1 per pixel: the mean distance of the samples that hit; 0 where none did
+    std::vector<float> coverage;   // 1 per pixel: the fraction of the samples that hit
+};
 class SamplerIntegrator : public Integrator {
   public:
     SamplerIntegrator(std::shared_ptr<const Camera> camera, std::shared_ptr<Sampler> sampler, const Bounds2i& pixelBounds,
@@ -764,6 +773,14 @@ class SamplerIntegrator : public Integrator {
     // (Render's bits there).  Synchronous, single device; a custom (table) sampler throws.  Starts a new
     // image: a RenderSamples pass cannot continue it.
     std::vector<int> RenderAdaptive(const Scene& scene, int minSamples, int samplesPerRound, float tolerance, float floor);
+    // Feature buffers, the side inputs of a denoiser (no reference counterpart; pbr_hip_render_aov): for
+    // samples [firstSample, firstSample + nSamples) of every pixel — the camera samples RenderSamples draws
+    // — the albedo, shading normal and distance of the first surface seen, added in sample order onto
+    // sums the integrator keeps on its device; *out receives the buffers over all samples so far.
+    // firstSample == 0 starts, any other value must continue where the last RenderFeatures call ended
+    // (its count is independent of RenderSamples').  Honours SetTiles: pixels outside the tiles are left 0.
+    // Synchronous, single device; a custom (table) sampler throws.
+    void RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out);
     // Uploads the scene to the integrator's device (BVHAccel build, lights, media); Render and Li
     // do it on first use.  The reference's SamplerIntegrator::Preprocess is a no-op hook.
     virtual void Preprocess(const Scene& scene, Sampler& sampler);
@@ -811,6 +828,9 @@ class SamplerIntegrator : public Integrator {
     struct Progressive;                  // RenderSamples: the carried sums and the pass's images, on the device
     std::shared_ptr<Progressive> prog;
     int samplesDone = 0;
+    struct Features;                     // RenderFeatures: the carried feature sums, on the device
+    std::shared_ptr<Features> feat;
+    int featuresDone = 0;
     std::vector<int> RenderPass(const Scene& scene, const char* who, int firstSample, int nSamples, const pbr_adaptive* adaptive);
 };
 class WhittedIntegrator : public SamplerIntegrator {   // Integrator/WhittedIntegrator.h

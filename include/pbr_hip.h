@@ -21,6 +21,8 @@
  *                           resumable passes over a carried per-pixel sum (progressive rendering)
  *   pbr_hip_render_adaptive — (none): those passes with a per-pixel stopping rule (adaptive sampling;
  *                           pbr_hip_adaptive_select and pbr_hip_render_passes_list are its two steps)
+ *   pbr_hip_render_aov    — (none): per-pixel albedo, coverage, normal and depth of the first surface the
+ *                           same camera samples see, in the same resumable passes (feature buffers)
  *   pbr_hip_destroy      — scene/integrator destructors
  *   pbr_hip_last_error    — (none; the reference fails silently)
  *   pbr_hip_sync          — (none; the reference's Render returns when the frame is done): waits
@@ -405,6 +407,50 @@ typedef struct pbr_adaptive_result {
  * keeps no state between calls: a checkpoint is accum plus counts.  `result` may be NULL. */
 int pbr_hip_render_adaptive(pbr_hip_ctx* ctx, const pbr_render_desc* desc, const pbr_adaptive* params, float* accum, int32_t* counts,
                             float* rgb_out, uint8_t* rgba_out, pbr_adaptive_result* result);
+
+/* ---- feature buffers (no reference counterpart) ----
+ * The side inputs a denoiser asks for beside a low-sample image: per pixel the albedo, normal and depth
+ * of the first surface each camera sample sees, summed over the same camera samples as the beauty image
+ * of pbr_hip_render_passes.  For pixel p and sample number s the sampler is positioned exactly as a
+ * render positions it (the sample index of (x, y, s), dimensions 0-4 through GetCameraSample, thin lens
+ * included; the render's own camera function).  The camera ray is traced to its closest hit.  A hit on a
+ * surface without a material is a medium boundary (the !isect.bsdf case of the three Li's) and is passed
+ * through as Li passes it — SpawnRay(ray.d), trace again — up to 1024 crossings; beyond that the frame
+ * fails through the device guard (PBR_E_UNSUPPORTED from this call or the next pbr_hip_sync), as a
+ * render does.  The sample's eight values (all 0 on a miss):
+ *     0-2  albedo, float32, nothing fused, from the material's parameters after their textures are
+ *          evaluated at the hit's (u, v) and after the material's own clamp to [0, inf): Matte Kd,
+ *          Plastic Kd, Mirror Kr, Glass Kt; Metal the conductor's reflectance at normal incidence per
+ *          channel, in this order: a = eta - 1; b = eta + 1; k2 = k * k; r = (a * a + k2) / (b * b + k2).
+ *          A sphere uses its material's constants.
+ *     3    hit: 1.0f
+ *     4-6  the shading normal ns of pbr_surface_hit: world space, as the intersection leaves it, not
+ *          flipped towards the camera
+ *     7    t: the ray parameter of the recorded hit; with crossings, the sum of the segments' t in order
+ *          (camera directions are unit length, so a distance)
+ * accum = PBR_AOV_CHANNELS floats per pixel in the descriptor's packed tile order.  A pass over samples
+ * [first_sample, first_sample + samples) continues each channel's sum in sample order with acc = acc + v
+ * (the rule of pbr_hip_render_passes), so any cut of the samples into passes leaves the bits of one
+ * pass; with first_sample == 0 accum is not read.  aov_out (or NULL) receives the image, 8 floats per
+ * pixel, with k = first_sample + samples samples done: channels 0-2 Σalbedo / k; 3 Σhit / k, the
+ * coverage; 4-6 Σns / k — an average, NOT renormalised to unit length; 7 Σt / Σhit where Σhit > 0, else 0.
+ * Conditions as pbr_hip_render_passes: outputs_on_device = 1, collect_stats = 0, accum a device pointer,
+ * aov_out a device pointer or NULL; a sample table returns PBR_E_UNSUPPORTED; desc->spp is the sampler's
+ * budget (Sobol: rounded up to a power of two) and first_sample + samples must not exceed it.  The
+ * descriptor's integrator, depth, roulette and light strategy are ignored; its camera, sampler, spp and
+ * tiles are used.  Asynchronous on desc->stream with the ordering of a pass: calls on one stream follow
+ * each other, a call on another stream drains the context first, and pbr_hip_wait_frame(ctx, stream, 0)
+ * orders another stream after the call.  PBR_E_INVALID: NULL ctx, desc or accum, samples < 1,
+ * first_sample < 0, a range above the budget.  A scene whose tree is too deep for the quad walk runs the
+ * per-lane binary walk. */
+#define PBR_AOV_CHANNELS 8
+int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int first_sample, int samples, float* accum, float* aov_out);
+/* How such a pass over n_pixels pixels is cut into kernel launches (a pure function: no context, no GPU
+ * call): consecutive ranges of the packed pixel order, each launch below 2^31 samples (C4's 8,294,400
+ * pixels at 1024 samples take four).  Up to max_launches ranges go to first_pixel[] / n_launch_pixels[]
+ * (either may be NULL when max_launches == 0); *n_launches is their total number. */
+int pbr_hip_plan_aov(int64_t n_pixels, int samples, int max_launches, int64_t* first_pixel, int64_t* n_launch_pixels,
+                     int* n_launches);
 
 /* ---- schedule (no reference counterpart) ----
  * How a frame is cut into launches on the device.  Every setting renders the same bits (the GPU

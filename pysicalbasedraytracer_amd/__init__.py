@@ -155,6 +155,35 @@ class HipRenderer:
         self._check(self.lib.pbr_hip_render_passes(self.ctx, C.byref(d), first_sample, samples_per_pass, n, accum_ptr,
                                                    rgb, rgba), "render_passes")
 
+    def render_aov(self, rdesc, first_sample, samples, accum_ptr, out_ptr=None, stream: int | None = None):
+        """A feature pass (pbr_hip_render_aov): for samples [first_sample, first_sample + samples) of every
+        pixel, the albedo (3), hit (1), shading normal (3) and distance (1) of the first surface the camera
+        sample sees, added in sample order onto accum (device, capi.AOV_CHANNELS float32 per pixel, packed
+        tile order; not read when first_sample == 0).  out_ptr (device, 8 float32 per pixel, or None)
+        receives the image over all samples so far: mean albedo, coverage, mean normal (not renormalised),
+        mean distance of the samples that hit.  rdesc.spp stays the whole budget; the descriptor's
+        integrator, depth and light strategy are not read.  Asynchronous, ordered as render_passes;
+        wait_frame(stream, 0) orders another stream after it."""
+        first_sample, samples = int(first_sample), int(samples)
+        if samples < 1:
+            raise ValueError("render_aov: samples must be >= 1")
+        if first_sample < 0:
+            raise ValueError("render_aov: first_sample must be >= 0")
+        if not accum_ptr:
+            raise ValueError("render_aov: accum is required (a device buffer of 8 float32 per pixel)")
+        if rdesc.sampler == capi.SAMPLER_TABLE:
+            raise ValueError("render_aov: no passes over a sample table")
+        budget = self.sample_budget(rdesc)
+        if first_sample + samples > budget:
+            raise ValueError(f"render_aov: samples [{first_sample}, {first_sample + samples}) run past the budget of "
+                             f"{budget} samples per pixel")
+        d = type(rdesc).from_buffer_copy(rdesc)   # (the caller's descriptor is left as it was: render_frames)
+        d.outputs_on_device = 1
+        d.stream = stream
+        d.collect_stats = 0
+        self._check(self.lib.pbr_hip_render_aov(self.ctx, C.byref(d), first_sample, samples, accum_ptr, out_ptr or None),
+                    "render_aov")
+
     @staticmethod
     def _check_rule(who, tolerance, floor):
         tolerance, floor = float(tolerance), float(floor)
@@ -410,9 +439,13 @@ class ProgressiveRender:
     Owns the accumulator of HipRenderer.render_passes as a torch tensor on the renderer's device
     ([n_pixels, 6] float32 in the descriptor's packed tile order: Σ Li.rgb, Σ Li.rgb²).  The image
     after k samples is the bits of a whole render whose sampler's first k samples are these; at
-    rdesc.spp samples it is HipRenderer.render's."""
+    rdesc.spp samples it is HipRenderer.render's.
 
-    def __init__(self, renderer: HipRenderer, rdesc, device=None):
+    features=True: every step also advances a feature accumulator ([n_pixels, 8] float32, the sums of
+    HipRenderer.render_aov) over the same samples; features() gives the denoiser inputs, and state() /
+    restore() carry it under the key "features"."""
+
+    def __init__(self, renderer: HipRenderer, rdesc, device=None, features=False):
         if rdesc.sampler == capi.SAMPLER_TABLE:
             raise ValueError("ProgressiveRender: no passes over a sample table")
         if rdesc.spp < 1:
@@ -423,7 +456,8 @@ class ProgressiveRender:
         self.n_pixels = HipRenderer.n_pixels(rdesc)
         self.samples_done = 0
         self._device = device
-        self._accum = self._rgb = self._rgba = self._stream = None
+        self._features = bool(features)
+        self._accum = self._rgb = self._rgba = self._stream = self._aov = self._aov_img = None
 
     def _check_step(self, n_samples, passes):
         n_samples, passes = int(n_samples), int(passes)
@@ -441,6 +475,9 @@ class ProgressiveRender:
             self._accum = torch.zeros((self.n_pixels, 6), dtype=torch.float32, device=dev)
             self._rgb = torch.empty((self.n_pixels, 3), dtype=torch.float32, device=dev)
             self._rgba = torch.empty((self.n_pixels, 4), dtype=torch.uint8, device=dev)
+            if self._features:
+                self._aov = torch.zeros((self.n_pixels, capi.AOV_CHANNELS), dtype=torch.float32, device=dev)
+                self._aov_img = torch.zeros((self.n_pixels, capi.AOV_CHANNELS), dtype=torch.float32, device=dev)
             # the passes run on a stream of their own (the library takes a real stream handle; torch's
             # default stream has none), ordered against the caller's current stream by events
             self._stream = torch.cuda.Stream(dev)
@@ -459,9 +496,24 @@ class ProgressiveRender:
         rgba = [None] * (passes - 1) + [self._rgba.data_ptr()]
         self.renderer.render_passes(self.rdesc, self.samples_done, n_samples, self._accum.data_ptr(), rgb, rgba,
                                     stream=self._stream.cuda_stream)
+        if self._features:   # (one feature pass over the step's samples, behind its passes on the same stream)
+            self.renderer.render_aov(self.rdesc, self.samples_done, n_samples * passes, self._aov.data_ptr(),
+                                     self._aov_img.data_ptr(), stream=self._stream.cuda_stream)
         current.wait_stream(self._stream)
         self.samples_done += n_samples * passes
         return self._rgb, self._rgba
+
+    def features(self) -> dict:
+        """The feature buffers over the samples done so far, as views of one device tensor (reused by the
+        next step): albedo [n, 3], coverage [n], normal [n, 3] (the mean shading normal, not renormalised),
+        depth [n] (the mean distance of the samples that hit; 0 where none did)."""
+        if not self._features:
+            raise ValueError("ProgressiveRender.features: constructed with features=False")
+        if self.samples_done < 1:
+            raise ValueError("ProgressiveRender.features needs at least one step")
+        self._buffers()
+        f = self._aov_img
+        return {"albedo": f[:, 0:3], "coverage": f[:, 3], "normal": f[:, 4:7], "depth": f[:, 7]}
 
     def variance(self):
         """Per-pixel, per-channel sample variance [n_pixels, 3] (device tensor) from the two carried
@@ -477,7 +529,10 @@ class ProgressiveRender:
     def state(self) -> dict:
         """A checkpoint: the accumulator as a numpy array and the samples done (waits for the device)."""
         self._buffers()
-        return {"samples_done": self.samples_done, "accum": self._accum.cpu().numpy().copy()}
+        st = {"samples_done": self.samples_done, "accum": self._accum.cpu().numpy().copy()}
+        if self._features:
+            st["features"] = self._aov.cpu().numpy().copy()
+        return st
 
     def restore(self, state: dict):
         """Resume from state(): the same descriptor on any renderer holding the same scene."""
@@ -487,8 +542,18 @@ class ProgressiveRender:
             raise ValueError(f"ProgressiveRender.restore: accumulator of shape {acc.shape}, expected {(self.n_pixels, 6)}")
         if done < 0 or done > self.budget:
             raise ValueError(f"ProgressiveRender.restore: {done} samples done outside the budget of {self.budget}")
+        feat = None
+        if self._features:
+            if "features" not in state:
+                raise ValueError("ProgressiveRender.restore: the state carries no feature accumulator")
+            feat = np.asarray(state["features"], dtype=np.float32)
+            if feat.shape != (self.n_pixels, capi.AOV_CHANNELS):
+                raise ValueError(f"ProgressiveRender.restore: feature accumulator of shape {feat.shape}, expected "
+                                 f"{(self.n_pixels, capi.AOV_CHANNELS)}")
         torch = self._buffers()
         self._accum.copy_(torch.from_numpy(np.ascontiguousarray(acc)))
+        if feat is not None:
+            self._aov.copy_(torch.from_numpy(np.ascontiguousarray(feat)))
         self.samples_done = done
 
 

@@ -281,6 +281,22 @@ def plan_chunks(integrator, n_pixels, spp, max_depth, n_lights=1, sky_light=Fals
     return out.as_dict()
 
 
+AOV_CHANNELS = 8   # PBR_AOV_CHANNELS: albedo rgb, hit, shading normal xyz, t
+
+
+def plan_aov(n_pixels, samples, lib=None) -> list:
+    """pbr_hip_plan_aov: the (first_pixel, n_pixels) launches a feature pass over n_pixels pixels of
+    `samples` samples each is cut into (no context, no GPU call)."""
+    fn = (lib or load_library()).pbr_hip_plan_aov
+    n = C.c_int(0)
+    if fn(int(n_pixels), int(samples), 0, None, None, C.byref(n)) != PBR_OK:
+        raise ValueError("plan_aov: n_pixels and samples must be >= 1")
+    first, count = (C.c_int64 * n.value)(), (C.c_int64 * n.value)()
+    if fn(int(n_pixels), int(samples), n.value, first, count, C.byref(n)) != PBR_OK:
+        raise ValueError("plan_aov: n_pixels and samples must be >= 1")
+    return [(int(first[i]), int(count[i])) for i in range(n.value)]
+
+
 # Every symbol include/pbr_hip.h declares, with its ctypes signature.
 EXPORTS = {
     "pbr_hip_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -301,6 +317,9 @@ EXPORTS = {
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbr_hip_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.POINTER(AdaptiveResult)]),
+    "pbr_hip_render_aov": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pbr_hip_plan_aov": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                   C.POINTER(C.c_int)]),
     "pbr_hip_get_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int)]),
     "pbr_hip_sampler_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -344,7 +363,7 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_set_schedule", "pbr_hip_sample_index", "pbr_hip_sample_dimensions",
                    "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk",
                    "pbr_hip_plan_chunks", "pbr_hip_last_chunks", "pbr_hip_adaptive_select", "pbr_hip_render_passes_list",
-                   "pbr_hip_render_adaptive")
+                   "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

@@ -24,6 +24,7 @@
 #include "pbr_device.h"
 #include "pbr_scene.h"
 #include "pbr_chunk_plan.h"
+#include "pbr_aov_plan.h"
 
 using namespace pbr;
 
@@ -675,6 +676,7 @@ __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
 #include "pbr_wavefront_path.h"
 #include "pbr_wavefront_volpath.h"
 #include "pbr_adaptive.h"
+#include "pbr_aov.h"
 
 // ---------------------------------------------------------------- introspection kernels
 __global__ void k_sampler_values(DeviceSampler smp, HaltonParams hp, int n, const int32_t* q, float* out) {
@@ -967,6 +969,7 @@ struct pbr_hip_ctx {
     HaltonTables halton;
     DevBuf dInfTex, dInfCF, dInfCC, dInfMF, dInfMC, dInfRec;
     DevBuf dTexels, dTextures, dTexMats;   // ImageTextures and the textured materials' parameters
+    DevBuf dAlbedo;                        // per material: the feature buffers' albedo (pbr_aov.h)
     DevBuf dNodes, dWide, dQuad, dTri, dInfo, dUV, dSph, dMat, dLights, dEnv, dCdf, dFunc, dMedia;
     DevBuf dPrimes, dRecips, dPrimeSums, dPerms, dPrimIds;
     DevBuf dSobol, dSobolHi, dSobolPix;  // active Sobol nibble tables (index bits 0-31, 32-51), pixel tables
@@ -2264,6 +2267,7 @@ int pbr_hip_upload_scene(pbr_hip_ctx* ctx, const pbr_scene_desc* desc) {
     HIP_TRY(ctx->dTexels.upload(h.texTexels, ctx->stream));
     HIP_TRY(ctx->dTextures.upload(h.textures, ctx->stream));
     HIP_TRY(ctx->dTexMats.upload(h.texMats, ctx->stream));
+    HIP_TRY(ctx->dAlbedo.upload(h.albedo, ctx->stream));
     int rc = upload_light_distribution(ctx, PBR_LIGHTS_UNIFORM);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2746,6 +2750,90 @@ int pbr_hip_render_adaptive(pbr_hip_ctx* ctx, const pbr_render_desc* d, const pb
     return PBR_OK;
 }
 
+int pbr_hip_plan_aov(int64_t n_pixels, int samples, int max_launches, int64_t* first_pixel, int64_t* n_launch_pixels, int* n_launches) {
+    if (n_pixels < 1 || samples < 1 || max_launches < 0 || !n_launches) return PBR_E_INVALID;
+    if (max_launches > 0 && (!first_pixel || !n_launch_pixels)) return PBR_E_INVALID;
+    const std::vector<AovLaunch> l = aov_launches(n_pixels, samples);
+    for (size_t i = 0; i < l.size() && (int)i < max_launches; ++i) {
+        first_pixel[i] = l[i].pix0;
+        n_launch_pixels[i] = l[i].nPix;
+    }
+    *n_launches = (int)l.size();
+    return PBR_OK;
+}
+
+int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sample, int samples, float* accum, float* aov_out) {
+    if (!ctx) return PBR_E_INVALID;
+    if (!d) return set_err(ctx, PBR_E_INVALID, "render_aov: null render desc");
+    if (!accum) return set_err(ctx, PBR_E_INVALID, "render_aov: accum must be a device buffer of 8 floats per pixel");
+    if (samples < 1) return set_err(ctx, PBR_E_INVALID, "render_aov: samples must be >= 1");
+    if (first_sample < 0) return set_err(ctx, PBR_E_INVALID, "render_aov: first_sample must be >= 0");
+    if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
+    if (d->sampler == PBR_SAMPLER_TABLE) return set_err(ctx, PBR_E_UNSUPPORTED, "render_aov: no passes over a sample table");
+    if (!d->outputs_on_device || d->collect_stats) return set_err(ctx, PBR_E_INVALID, "render_aov: device outputs, no stats");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // as a render: a scene with material-less primitives can trip the crossing bound, so its earlier
+    // asynchronous frame is waited for and checked; every other call stays queued back to back
+    if (ctx->host.anyNoMaterial) {
+        if (int rc = drain(ctx)) return rc;
+    }
+    if (int rc = check_guard(ctx)) return rc;
+    hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
+    // the camera, sampler, spp and tiles of the descriptor; its integrator, depth, roulette and light
+    // strategy are not read (make_params validates them, so they are set to values that always pass)
+    pbr_render_desc dd = *d;
+    dd.integrator = PBR_INTEGRATOR_PATH;
+    dd.max_depth = 0;
+    dd.light_strategy = ctx->curStrategy;
+    AovParams A;
+    std::memset(&A, 0, sizeof(A));
+    if (int rc = make_params(ctx, &dd, &A.P)) return rc;
+    KParams& P = A.P;   // (P.spp is the sampler's budget until here)
+    if ((long long)first_sample + samples > (long long)P.spp)
+        return set_err(ctx, PBR_E_INVALID, "render_aov: samples [" + std::to_string(first_sample) + ", " +
+                       std::to_string((long long)first_sample + samples) + ") run past the budget of " + std::to_string(P.spp) +
+                       " samples per pixel");
+    P.spp = samples;
+    P.ppb = aov_pixels_per_block(samples);
+    P.smp.passFirst = first_sample;
+    long long npx = 0;
+    if (int rc = frame_tiles(ctx, d, s, &npx, &P.nTiles)) return rc;   // (another stream: drains the context first)
+    P.tiles = (const int4*)ctx->dTiles.p;
+    P.tileStart = (const long long*)ctx->dTileStart.p;
+    P.nPixels = npx;
+    A.accum = accum;
+    A.out = aov_out;
+    A.albedo = (const float4*)ctx->dAlbedo.p;
+    const bool tex = !ctx->host.texMats.empty(), binary = P.S.binaryWalk != 0;
+    const int kind = tex ? KP_AOV_TEX : KP_AOV;
+    ctx->batchFrames = 0;   // (set when the pass is queued)
+    ctx->lane0 = s;
+    ctx->lastOwnLane0 = false;
+    ctx->lastPlan = wf_no_chunks();
+    for (const AovLaunch& l : aov_launches(npx, samples)) {
+        A.pix0 = l.pix0;
+        A.pixEnd = l.pix0 + l.nPix;
+        const dim3 grid((unsigned)((l.nPix + P.ppb - 1) / P.ppb)), blk(kAovBlock);
+        PROF_LAUNCH(kind, s,
+            if (tex) { if (binary) hipLaunchKernelGGL((k_aov<true, true>), grid, blk, 0, s, A); else hipLaunchKernelGGL((k_aov<true, false>), grid, blk, 0, s, A); }
+            else { if (binary) hipLaunchKernelGGL((k_aov<false, true>), grid, blk, 0, s, A); else hipLaunchKernelGGL((k_aov<false, false>), grid, blk, 0, s, A); });
+    }
+    HIP_TRY(hipGetLastError());
+    prof_host(ctx, kind, 0, (unsigned long long)npx * (unsigned long long)samples);
+    prof_host(ctx, kind, 1, (unsigned long long)npx);
+    if (first_sample > 0) prof_host(ctx, kind, 2, (unsigned long long)npx);
+    if (aov_out) prof_host(ctx, kind, 3, (unsigned long long)npx);
+    if (int rc = wf_frame_done(ctx, s, 0, 0u)) return rc;
+    ctx->batchFrames = 1;
+    // the guard word, as at the end of every frame (render_impl)
+    HIP_TRY(hipMemcpyAsync(ctx->guardHost, ctx->dGuard.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(ctx->evGuard, s));
+    ctx->guardPending = true;
+    ctx->inFlight = true;
+    ctx->lastStream = s;
+    return PBR_OK;
+}
+
 int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f) {
     if (!ctx) return PBR_E_INVALID;
     if (f < 0 || f >= ctx->batchFrames) return set_err(ctx, PBR_E_INVALID, "wait_frame: no such frame in the last batch");
@@ -2847,7 +2935,7 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
     static const char* kNames[KP_COUNT] = {
         "k_wf_camera_extend", "k_wf_shade", "k_wf_shadow", "k_wf_extend", "k_wf_finish",
         "k_wfp_camera_extend", "k_wfp_shade", "k_wfp_shadow", "k_wfp_probe", "k_wfp_resolve", "k_wfp_finish",
-        "k_wfv_shade", "k_wfv_tr", "k_wfv_resolve", "k_render", "k_wf_shade_l0"};
+        "k_wfv_shade", "k_wfv_tr", "k_wfv_resolve", "k_render", "k_wf_shade_l0", "k_aov", "k_aov_tex"};
     unsigned long long c[KP_COUNT][kProfFields];
     std::memset(c, 0, sizeof(c));
     if (ctx->profOn) HIP_TRY(hipMemcpy(c, ctx->dProf.p, sizeof(c), hipMemcpyDeviceToHost));
@@ -2889,6 +2977,8 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         case KP_WFV_SHADE: return 52 * f[0] + 36 * f[5] + 16 * (f[0] - f[4]) + 84 * f[1] + 36 * f[2] + 80 * f[3] + 68 * f[4];
         case KP_WFV_TR: return 100 * f[0];
         case KP_WFV_RESOLVE: return 140 * f[0];
+        // f[1] pixels: the sums written; f[2] of them continue (the sums read); f[3] write the image
+        case KP_AOV: case KP_AOV_TEX: return 32 * (f[1] + f[2] + f[3]);
         default: return 16 * f[1];                                             // megakernel: the film output
         }
     };

@@ -155,4 +155,26 @@ PBR_HD bool material_template(const MatParams& m, bool multi, MatTemplate* out) 
     }
 }
 
+// The albedo the feature buffers record for a material (pbr_hip_render_aov), from the
+// parameters with their textures evaluated and after the material's own clamp: Matte and Plastic Kd,
+// Mirror Kr, Glass Kt, Metal the conductor's reflectance at normal incidence.  False: no material.
+PBR_HD bool material_albedo(const MatParams& m, float* out) {
+    out[0] = out[1] = out[2] = 0.f;
+    switch (m.type) {
+    case 1: case 5: mt_clamp3(out, m.Kd); return true;
+    case 2: mt_clamp3(out, m.Kr); return true;
+    case 3: mt_clamp3(out, m.Kt); return true;
+    case 4:
+        for (int i = 0; i < 3; ++i) {
+            const float a = m.metal_eta[i] - 1.f, b = m.metal_eta[i] + 1.f, k2 = m.metal_k[i] * m.metal_k[i];
+            out[i] = (a * a + k2) / (b * b + k2);
+        }
+        return true;
+    default:
+        return false;
+    }
+}
+// The texture slot (pbr_texture_slot) that albedo is read from, or -1 (Metal, no material).
+PBR_HD int material_albedo_slot(int type) { return (type == 1 || type == 5) ? 0 : (type == 2 ? 2 : (type == 3 ? 3 : -1)); }
+
 }  // namespace pbr

@@ -38,6 +38,7 @@ enum ProfKind {
     KP_WFP_CAMERA, KP_WFP_SHADE, KP_WFP_SHADOW, KP_WFP_PROBE, KP_WFP_RESOLVE, KP_WFP_FINISH,
     KP_WFV_SHADE, KP_WFV_TR, KP_WFV_RESOLVE, KP_MEGA,
     KP_WF_SHADE0,   // k_wf_shade's fused level-0 launches (camera rays traced in the shade): own family
+    KP_AOV, KP_AOV_TEX,   // feature passes (pbr_aov.h): the untextured and the textured instantiations
     KP_COUNT
 };
 constexpr int kProfFields = 8;

@@ -1580,6 +1580,92 @@ std::vector<int> SamplerIntegrator::RenderAdaptive(const Scene& scene, int minSa
     return RenderPass(scene, "RenderAdaptive", 0, 0, &a);
 }
 
+// Device buffers of RenderFeatures: 8 floats of sums and 8 floats of image per pixel.
+struct SamplerIntegrator::Features {
+    int device = 0;
+    size_t npx = 0;
+    float* accum = nullptr;
+    float* image = nullptr;
+    ~Features() {
+        if (hipSetDevice(device) != hipSuccess) return;
+        if (accum) (void)hipFree(accum);
+        if (image) (void)hipFree(image);
+    }
+};
+
+void SamplerIntegrator::RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out) {
+    const std::string who("RenderFeatures");
+    if (firstSample < 0 || nSamples < 1) throw std::invalid_argument(who + ": firstSample >= 0 and nSamples >= 1");
+    if (!out) throw std::invalid_argument(who + ": out == nullptr");
+    if (!devices.empty()) throw std::invalid_argument(who + ": one device (SetDevice), not SetDevices");
+    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
+    if (!cam) throw std::invalid_argument(who + ": only PerspectiveCamera is on the GPU path");
+    check_sampler(*sampler, *cam, "RenderFeatures");
+    if (sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
+        throw std::invalid_argument(who + ": a custom sampler's values go to the device as a whole frame's table; "
+                                    "sample passes need HaltonSampler or SobolSampler");
+    if (firstSample != 0 && (!feat || firstSample != featuresDone))
+        throw std::invalid_argument(who + ": firstSample " + std::to_string(firstSample) + " does not continue the " +
+                                    std::to_string(feat ? featuresDone : 0) + " samples done");
+    const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;   // the reference reads pMax only
+    if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
+        throw std::invalid_argument(who + ": pixelBounds outside the camera raster");
+    ensure_scene(scene);
+    auto flat = FlattenScene(scene, cam->medium);   // for the camera medium's index
+    pbr_render_desc rd;
+    std::memset(&rd, 0, sizeof(rd));
+    rd.integrator = IntegratorType();   // (not read by a feature pass)
+    rd.max_depth = MaxDepth();
+    rd.rr_threshold = RRThreshold();
+    rd.light_strategy = LightStrategy();
+    rd.sampler = sampler->DeviceSampler();
+    rd.spp = (int)sampler->samplesPerPixel;
+    camera_desc(*cam, &rd.camera);
+    rd.camera.medium = MediumIndex(*flat, cam->medium);
+    std::vector<pbr_tile> tl;
+    if (!tiles.empty()) {
+        for (const Bounds2i& b : tiles) tl.push_back({b.pMin.x, b.pMin.y, b.pMax.x, b.pMax.y});
+    } else {
+        tl.push_back({0, 0, W, H});
+    }
+    rd.n_tiles = (int)tl.size();
+    rd.tiles = tl.data();
+    rd.outputs_on_device = 1;
+    size_t npx = 0;
+    for (const pbr_tile& t : tl) npx += (size_t)(t.x1 - t.x0) * (t.y1 - t.y0);
+    hip_check(hipSetDevice(device), "hipSetDevice");
+    if (!feat || feat->npx != npx || feat->device != device) {
+        if (firstSample != 0) throw std::invalid_argument(who + ": the tiles changed since the last call");
+        feat = std::make_shared<Features>();
+        feat->device = device;
+        feat->npx = npx;
+        hip_check(hipMalloc((void**)&feat->accum, std::max<size_t>(1, npx) * PBR_AOV_CHANNELS * sizeof(float)), "hipMalloc");
+        hip_check(hipMalloc((void**)&feat->image, std::max<size_t>(1, npx) * PBR_AOV_CHANNELS * sizeof(float)), "hipMalloc");
+    }
+    check(ctx, pbr_hip_render_aov(ctx, &rd, firstSample, nSamples, feat->accum, feat->image), "pbr_hip_render_aov");
+    check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
+    featuresDone = firstSample + nSamples;
+    std::vector<float> img(npx * PBR_AOV_CHANNELS);
+    hip_check(hipMemcpy(img.data(), feat->image, img.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+    out->width = W;
+    out->height = H;
+    out->albedo.assign((size_t)W * H * 3, 0.f);
+    out->normal.assign((size_t)W * H * 3, 0.f);
+    out->depth.assign((size_t)W * H, 0.f);
+    out->coverage.assign((size_t)W * H, 0.f);
+    size_t k = 0;
+    for (const pbr_tile& t : tl)
+        for (int y = t.y0; y < t.y1; ++y)
+            for (int x = t.x0; x < t.x1; ++x, ++k) {
+                if (x >= W || y >= H) continue;   // (a tile may reach beyond the pixel bounds, inside the raster)
+                const float* v = &img[k * PBR_AOV_CHANNELS];
+                const size_t p = (size_t)y * W + x;
+                for (int c = 0; c < 3; ++c) { out->albedo[3 * p + c] = v[c]; out->normal[3 * p + c] = v[4 + c]; }
+                out->coverage[p] = v[3];
+                out->depth[p] = v[7];
+            }
+}
+
 // One pass of RenderSamples, or (adaptive != nullptr) a whole adaptive render from sample 0; returns
 // the adaptive render's per-pixel sample counts in packed tile order.
 std::vector<int> SamplerIntegrator::RenderPass(const Scene& scene, const char* whoName, int firstSample, int nSamples,
