@@ -825,11 +825,11 @@ class SamplerIntegrator : public Integrator {
     struct MultiGPU;
     std::shared_ptr<MultiGPU> multi;
     void RenderMulti(const Scene& scene, double& timeConsume);
-    struct Progressive;                  // RenderSamples: the carried sums and the pass's images, on the device
-    std::shared_ptr<Progressive> prog;
+    struct FrameRequest;                 // what every render entry point asks the device for (pbr_host.cpp)
+    struct PassBuffers;                  // the sums and images sample passes carry from call to call, on the device
+    std::shared_ptr<PassBuffers> prog;   // RenderSamples
     int samplesDone = 0;
-    struct Features;                     // RenderFeatures: the carried feature sums, on the device
-    std::shared_ptr<Features> feat;
+    std::shared_ptr<PassBuffers> feat;   // RenderFeatures
     int featuresDone = 0;
     std::vector<int> RenderPass(const Scene& scene, const char* who, int firstSample, int nSamples, const pbr_adaptive* adaptive);
 };

@@ -91,21 +91,34 @@ class HipRenderer:
         """n frames of one descriptor into device buffers (pbr_hip_render_frames): their chunks
         continue one rotation over the lanes with no join between frames.  Asynchronous; `stream`
         reaches its tail when every frame is done; wait_frame orders another stream after one."""
-        rgb_ptrs, rgba_ptrs = list(rgb_ptrs or []), list(rgba_ptrs or [])
-        if rgb_ptrs and rgba_ptrs and len(rgb_ptrs) != len(rgba_ptrs):
-            raise ValueError(f"render_frames: {len(rgb_ptrs)} float outputs but {len(rgba_ptrs)} RGBA8 outputs")
+        rgb_ptrs, rgba_ptrs = self._out_lists("render_frames", rgb_ptrs, rgba_ptrs)
         n = max(len(rgb_ptrs), len(rgba_ptrs))
         if n == 0:
             raise ValueError("render_frames: no output buffers")
-        rgb = (C.c_void_p * n)(*[p or None for p in rgb_ptrs]) if rgb_ptrs else None
-        rgba = (C.c_void_p * n)(*[p or None for p in rgba_ptrs]) if rgba_ptrs else None
-        # the caller's descriptor is left as it was: the batch's settings go on a copy (its tile
-        # pointer still refers to the caller's arrays, which rdesc keeps alive for this call)
+        self._check(self.lib.pbr_hip_render_frames(self.ctx, C.byref(self._device_desc(rdesc, stream)), n,
+                                                   self._ptr_array(rgb_ptrs), self._ptr_array(rgba_ptrs)), "render_frames")
+
+    @staticmethod
+    def _out_lists(who, rgb_ptrs, rgba_ptrs):
+        rgb_ptrs, rgba_ptrs = list(rgb_ptrs or []), list(rgba_ptrs or [])
+        if rgb_ptrs and rgba_ptrs and len(rgb_ptrs) != len(rgba_ptrs):
+            raise ValueError(f"{who}: {len(rgb_ptrs)} float outputs but {len(rgba_ptrs)} RGBA8 outputs")
+        return rgb_ptrs, rgba_ptrs
+
+    @staticmethod
+    def _ptr_array(ptrs):
+        return (C.c_void_p * len(ptrs))(*[p or None for p in ptrs]) if ptrs else None
+
+    @staticmethod
+    def _device_desc(rdesc, stream):
+        """What the asynchronous entry points run: device outputs on `stream`, no stats.  The caller's
+        descriptor is left as it was: the settings go on a copy (its tile pointer still refers to the
+        caller's arrays, which rdesc keeps alive for the call)."""
         d = type(rdesc).from_buffer_copy(rdesc)
         d.outputs_on_device = 1
         d.stream = stream
         d.collect_stats = 0
-        self._check(self.lib.pbr_hip_render_frames(self.ctx, C.byref(d), n, rgb, rgba), "render_frames")
+        return d
 
     @staticmethod
     def sample_budget(rdesc) -> int:
@@ -114,6 +127,29 @@ class HipRenderer:
         if rdesc.sampler == capi.SAMPLER_SOBOL and spp > 0:
             spp = 1 << (spp - 1).bit_length()
         return spp
+
+    @staticmethod
+    def _pass_budget(who, rdesc) -> int:
+        if rdesc.sampler == capi.SAMPLER_TABLE:
+            raise ValueError(f"{who}: no passes over a sample table")
+        return HipRenderer.sample_budget(rdesc)
+
+    @staticmethod
+    def _check_pass(who, rdesc, first_sample, samples, n_passes, accum_ptr, accum_floats, samples_arg="samples"):
+        """A window of n_passes passes of `samples` samples from first_sample, refused before any library
+        call unless it lies in the sampler's budget; returns the three as ints, and the budget."""
+        first_sample, samples, n_passes = int(first_sample), int(samples), int(n_passes)
+        if samples < 1:
+            raise ValueError(f"{who}: {samples_arg} must be >= 1")
+        if first_sample < 0:
+            raise ValueError(f"{who}: first_sample must be >= 0")
+        if not accum_ptr:
+            raise ValueError(f"{who}: accum is required (a device buffer of {accum_floats} float32 per pixel)")
+        budget = HipRenderer._pass_budget(who, rdesc)
+        end = first_sample + n_passes * samples
+        if end > budget:
+            raise ValueError(f"{who}: samples [{first_sample}, {end}) run past the budget of {budget} samples per pixel")
+        return first_sample, samples, n_passes, budget
 
     def render_passes(self, rdesc, first_sample, samples_per_pass, accum_ptr, rgb_ptrs=None, rgba_ptrs=None,
                       n_passes=None, stream: int | None = None):
@@ -124,36 +160,18 @@ class HipRenderer:
         a list, or an entry, may be None).  rdesc.spp stays the whole budget.  n_passes defaults to the
         length of the output lists.  Asynchronous, as render_frames; wait_frame(stream, p) orders
         another stream after pass p."""
-        rgb_ptrs, rgba_ptrs = list(rgb_ptrs or []), list(rgba_ptrs or [])
-        if rgb_ptrs and rgba_ptrs and len(rgb_ptrs) != len(rgba_ptrs):
-            raise ValueError(f"render_passes: {len(rgb_ptrs)} float outputs but {len(rgba_ptrs)} RGBA8 outputs")
+        rgb_ptrs, rgba_ptrs = self._out_lists("render_passes", rgb_ptrs, rgba_ptrs)
         n = max(len(rgb_ptrs), len(rgba_ptrs)) if n_passes is None else int(n_passes)
         if n < 1:
             raise ValueError("render_passes: no passes (give n_passes or output buffers)")
         for name, ptrs in (("rgb_ptrs", rgb_ptrs), ("rgba_ptrs", rgba_ptrs)):
             if ptrs and len(ptrs) != n:
                 raise ValueError(f"render_passes: {len(ptrs)} {name} for {n} passes")
-        first_sample, samples_per_pass = int(first_sample), int(samples_per_pass)
-        if samples_per_pass < 1:
-            raise ValueError("render_passes: samples_per_pass must be >= 1")
-        if first_sample < 0:
-            raise ValueError("render_passes: first_sample must be >= 0")
-        if not accum_ptr:
-            raise ValueError("render_passes: accum is required (a device buffer of 6 float32 per pixel)")
-        if rdesc.sampler == capi.SAMPLER_TABLE:
-            raise ValueError("render_passes: no passes over a sample table")
-        budget = self.sample_budget(rdesc)
-        if first_sample + n * samples_per_pass > budget:
-            raise ValueError(f"render_passes: samples [{first_sample}, {first_sample + n * samples_per_pass}) run past "
-                             f"the budget of {budget} samples per pixel")
-        rgb = (C.c_void_p * n)(*[p or None for p in rgb_ptrs]) if rgb_ptrs else None
-        rgba = (C.c_void_p * n)(*[p or None for p in rgba_ptrs]) if rgba_ptrs else None
-        d = type(rdesc).from_buffer_copy(rdesc)   # (the caller's descriptor is left as it was: render_frames)
-        d.outputs_on_device = 1
-        d.stream = stream
-        d.collect_stats = 0
+        first_sample, samples_per_pass, n, _ = self._check_pass("render_passes", rdesc, first_sample, samples_per_pass, n,
+                                                                accum_ptr, 6, samples_arg="samples_per_pass")
+        d = self._device_desc(rdesc, stream)
         self._check(self.lib.pbr_hip_render_passes(self.ctx, C.byref(d), first_sample, samples_per_pass, n, accum_ptr,
-                                                   rgb, rgba), "render_passes")
+                                                   self._ptr_array(rgb_ptrs), self._ptr_array(rgba_ptrs)), "render_passes")
 
     def render_aov(self, rdesc, first_sample, samples, accum_ptr, out_ptr=None, stream: int | None = None):
         """A feature pass (pbr_hip_render_aov): for samples [first_sample, first_sample + samples) of every
@@ -164,23 +182,8 @@ class HipRenderer:
         mean distance of the samples that hit.  rdesc.spp stays the whole budget; the descriptor's
         integrator, depth and light strategy are not read.  Asynchronous, ordered as render_passes;
         wait_frame(stream, 0) orders another stream after it."""
-        first_sample, samples = int(first_sample), int(samples)
-        if samples < 1:
-            raise ValueError("render_aov: samples must be >= 1")
-        if first_sample < 0:
-            raise ValueError("render_aov: first_sample must be >= 0")
-        if not accum_ptr:
-            raise ValueError("render_aov: accum is required (a device buffer of 8 float32 per pixel)")
-        if rdesc.sampler == capi.SAMPLER_TABLE:
-            raise ValueError("render_aov: no passes over a sample table")
-        budget = self.sample_budget(rdesc)
-        if first_sample + samples > budget:
-            raise ValueError(f"render_aov: samples [{first_sample}, {first_sample + samples}) run past the budget of "
-                             f"{budget} samples per pixel")
-        d = type(rdesc).from_buffer_copy(rdesc)   # (the caller's descriptor is left as it was: render_frames)
-        d.outputs_on_device = 1
-        d.stream = stream
-        d.collect_stats = 0
+        first_sample, samples, _, _ = self._check_pass("render_aov", rdesc, first_sample, samples, 1, accum_ptr, 8)
+        d = self._device_desc(rdesc, stream)
         self._check(self.lib.pbr_hip_render_aov(self.ctx, C.byref(d), first_sample, samples, accum_ptr, out_ptr or None),
                     "render_aov")
 
@@ -222,37 +225,21 @@ class HipRenderer:
         (device int32, ascending packed pixel indices) only (pbr_hip_render_passes_list).  accum, rgb
         and rgba are whole-frame device buffers; entries of unlisted pixels are not written.  Waits for
         the list's run count, then queues the pass as render_passes does."""
-        first_sample, samples, n_list = int(first_sample), int(samples), int(n_list)
-        if samples < 1:
-            raise ValueError("render_passes_list: samples must be >= 1")
-        if first_sample < 0:
-            raise ValueError("render_passes_list: first_sample must be >= 0")
+        first_sample, samples, _, _ = self._check_pass("render_passes_list", rdesc, first_sample, samples, 1, accum_ptr, 6)
+        n_list = int(n_list)
         if n_list < 0 or n_list > self.n_pixels(rdesc):
             raise ValueError(f"render_passes_list: n_list {n_list} outside [0, {self.n_pixels(rdesc)}]")
         if n_list and not list_ptr:
             raise ValueError("render_passes_list: list is required (a device buffer of int32 pixel indices)")
-        if not accum_ptr:
-            raise ValueError("render_passes_list: accum is required (a device buffer of 6 float32 per pixel)")
-        if rdesc.sampler == capi.SAMPLER_TABLE:
-            raise ValueError("render_passes_list: no passes over a sample table")
-        budget = self.sample_budget(rdesc)
-        if first_sample + samples > budget:
-            raise ValueError(f"render_passes_list: samples [{first_sample}, {first_sample + samples}) run past the budget "
-                             f"of {budget} samples per pixel")
-        d = type(rdesc).from_buffer_copy(rdesc)   # (the caller's descriptor is left as it was: render_frames)
-        d.outputs_on_device = 1
-        d.stream = stream
-        d.collect_stats = 0
+        d = self._device_desc(rdesc, stream)
         self._check(self.lib.pbr_hip_render_passes_list(self.ctx, C.byref(d), first_sample, samples, list_ptr or None, n_list,
                                                         accum_ptr, rgb_ptr or None, rgba_ptr or None), "render_passes_list")
 
     @staticmethod
     def _check_adaptive(who, rdesc, min_samples, samples_per_round, tolerance, floor):
-        if rdesc.sampler == capi.SAMPLER_TABLE:
-            raise ValueError(f"{who}: no passes over a sample table")
+        budget = HipRenderer._pass_budget(who, rdesc)
         if rdesc.spp < 1:
             raise ValueError(f"{who}: rdesc.spp (the sample budget) must be >= 1")
-        budget = HipRenderer.sample_budget(rdesc)
         min_samples, samples_per_round = int(min_samples), int(samples_per_round)
         if min_samples < 2 or min_samples > budget:
             raise ValueError(f"{who}: min_samples {min_samples} outside [2, {budget}] (the budget)")
@@ -270,10 +257,7 @@ class HipRenderer:
         a = self._check_adaptive("render_adaptive", rdesc, min_samples, samples_per_round, tolerance, floor)
         if not accum_ptr or not counts_ptr:
             raise ValueError("render_adaptive: accum and counts are required (device buffers)")
-        d = type(rdesc).from_buffer_copy(rdesc)
-        d.outputs_on_device = 1
-        d.stream = stream
-        d.collect_stats = 0
+        d = self._device_desc(rdesc, stream)
         res = capi.AdaptiveResult()
         self._check(self.lib.pbr_hip_render_adaptive(self.ctx, C.byref(d), C.byref(a), accum_ptr, counts_ptr, rgb_ptr or None,
                                                      rgba_ptr or None, C.byref(res)), "render_adaptive")
@@ -446,13 +430,11 @@ class ProgressiveRender:
     restore() carry it under the key "features"."""
 
     def __init__(self, renderer: HipRenderer, rdesc, device=None, features=False):
-        if rdesc.sampler == capi.SAMPLER_TABLE:
-            raise ValueError("ProgressiveRender: no passes over a sample table")
+        self.budget = HipRenderer._pass_budget("ProgressiveRender", rdesc)
         if rdesc.spp < 1:
             raise ValueError("ProgressiveRender: rdesc.spp (the sample budget) must be >= 1")
         self.renderer = renderer
         self.rdesc = rdesc
-        self.budget = HipRenderer.sample_budget(rdesc)
         self.n_pixels = HipRenderer.n_pixels(rdesc)
         self.samples_done = 0
         self._device = device

@@ -1910,6 +1910,53 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
     return rotate ? wf_join(ctx, s, ch.lanes) : PBR_OK;
 }
 
+// The sampler's samplesPerPixel for a descriptor's spp, the budget of its sample passes: SobolSampler
+// rounds spp up to a power of two (GlobalSampler(RoundUpPow2(spp)), Sobol.h).
+long long sampler_spp(int sampler, int spp) {
+    long long n = spp;
+    if (sampler == PBR_SAMPLER_SOBOL)
+        for (n = 1; n < spp;) n <<= 1;
+    return n;
+}
+
+// The stream a call runs on: the descriptor's, or the context's own.
+hipStream_t call_stream(pbr_hip_ctx* ctx, const pbr_render_desc* d) { return d->stream ? (hipStream_t)d->stream : ctx->stream; }
+
+// The end of every frame, pass and guarded query: the guard word is copied out (4 B, asynchronous), so a
+// bound or a full traversal stack fails this call (synchronous ones, which wait for `s` and then
+// check_guard) or the next one / pbr_hip_sync (async: the call returns with its work in flight on `s`),
+// and a bit is never left behind to fail an unrelated later frame.
+int hand_off_guard(pbr_hip_ctx* ctx, hipStream_t s, bool async) {
+    HIP_TRY(hipMemcpyAsync(ctx->guardHost, ctx->dGuard.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(ctx->evGuard, s));
+    ctx->guardPending = true;
+    if (async) {
+        ctx->inFlight = true;
+        ctx->lastStream = s;
+    }
+    return PBR_OK;
+}
+
+// A query's round trip through the context's scratch buffers on its stream: the host span a (and b,
+// packed behind it) in, launch(a on the device, b on the device, the output) → int when n > 0, outBytes
+// back to `out`, and the stream waited for.
+template <class Launch>
+int scratch_round_trip(pbr_hip_ctx* ctx, int n, const void* a, size_t aBytes, const void* b, size_t bBytes, void* out,
+                       size_t outBytes, Launch launch) {
+    HIP_TRY(ctx->dScratchIn.ensure(aBytes + bBytes));
+    HIP_TRY(ctx->dScratchOut.ensure(outBytes));
+    char* in = (char*)ctx->dScratchIn.p;
+    HIP_TRY(hipMemcpyAsync(in, a, aBytes, hipMemcpyHostToDevice, ctx->stream));
+    if (b) HIP_TRY(hipMemcpyAsync(in + aBytes, b, bBytes, hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0) {
+        if (int rc = launch((const char*)in, (const char*)in + aBytes, ctx->dScratchOut.p)) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PBR_OK;
+}
+
 // The integrator, sampler and scene parameters of a render descriptor (validated): shared by
 // pbr_hip_render and the per-ray pbr_hip_li.
 int make_params(pbr_hip_ctx* ctx, const pbr_render_desc* d, KParams* out) {
@@ -1921,12 +1968,9 @@ int make_params(pbr_hip_ctx* ctx, const pbr_render_desc* d, KParams* out) {
         return set_err(ctx, PBR_E_INVALID, "unknown integrator");
     if (d->sampler != PBR_SAMPLER_HALTON && d->sampler != PBR_SAMPLER_SOBOL && d->sampler != PBR_SAMPLER_TABLE)
         return set_err(ctx, PBR_E_INVALID, "unknown sampler");
-    // SobolSampler rounds spp up to a power of two (GlobalSampler(RoundUpPow2(spp)), Sobol.h)
-    int spp = d->spp;
+    if (sampler_spp(d->sampler, d->spp) > 0x7fffffffLL) return set_err(ctx, PBR_E_UNSUPPORTED, "spp too large for 32-bit sample indices");
+    const int spp = (int)sampler_spp(d->sampler, d->spp);
     if (d->sampler == PBR_SAMPLER_SOBOL) {
-        int p2 = 1;
-        while (p2 < spp) p2 <<= 1;
-        spp = p2;
         int res = 1, m = 0;
         while (res < std::max(d->camera.width, d->camera.height)) { res <<= 1; ++m; }
         // pbrt-v3's SobolSampleFloat reads one 52-column matrix per dimension: indices below 2^52
@@ -1993,16 +2037,12 @@ int pbr_hip_query(pbr_hip_ctx* ctx, int n, const float* rays, int any_hit, int p
     if (int rc = drain(ctx)) return rc;
     if (n == 0) return PBR_OK;
     const int slot = prim >= 0 ? ctx->host.slotOf[prim] : -1;
-    HIP_TRY(ctx->dScratchIn.ensure((size_t)n * 7 * sizeof(float)));
-    HIP_TRY(ctx->dScratchOut.ensure((size_t)n * sizeof(pbr_surface_hit)));
-    HIP_TRY(hipMemcpyAsync(ctx->dScratchIn.p, rays, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_query, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, device_scene(ctx),
-                       (const int32_t*)ctx->dPrimIds.p, n, (const float*)ctx->dScratchIn.p, any_hit ? 1 : 0, slot,
-                       (pbr_surface_hit*)ctx->dScratchOut.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, (size_t)n * sizeof(pbr_surface_hit), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PBR_OK;
+    return scratch_round_trip(ctx, n, rays, (size_t)n * 7 * sizeof(float), nullptr, 0, out, (size_t)n * sizeof(pbr_surface_hit),
+                              [&](const char* in, const char*, void* o) {
+        hipLaunchKernelGGL(k_query, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, device_scene(ctx),
+                           (const int32_t*)ctx->dPrimIds.p, n, (const float*)in, any_hit ? 1 : 0, slot, (pbr_surface_hit*)o);
+        return PBR_OK;
+    });
 }
 
 int pbr_hip_bounds(pbr_hip_ctx* ctx, int prim, float* out6) {
@@ -2043,27 +2083,18 @@ int pbr_hip_li(pbr_hip_ctx* ctx, const pbr_render_desc* d, int n, const float* r
             q[4 * i + 2] < 0 || q[4 * i + 2] >= P.spp || q[4 * i + 3] < 0)
             return set_err(ctx, PBR_E_INVALID, "pixel / sample / dimension out of range");
     }
-    const size_t rb = (size_t)n * 7 * 4, qb = (size_t)n * 16, ob = (size_t)n * 12;
-    HIP_TRY(ctx->dScratchIn.ensure(rb + qb));
-    HIP_TRY(ctx->dScratchOut.ensure(ob));
-    char* in = (char*)ctx->dScratchIn.p;
-    HIP_TRY(hipMemcpyAsync(in, rays, rb, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(in + rb, q, qb, hipMemcpyHostToDevice, ctx->stream));
-    const dim3 g((n + 63) / 64), b(64);
-    float* o = (float*)ctx->dScratchOut.p;
-    const int32_t* qd = (const int32_t*)(in + rb);
-    if (d->integrator == PBR_INTEGRATOR_WHITTED) hipLaunchKernelGGL(k_li<PBR_INTEGRATOR_WHITTED>, g, b, 0, ctx->stream, P, n, (const float*)in, qd, o);
-    else if (d->integrator == PBR_INTEGRATOR_PATH) hipLaunchKernelGGL(k_li<PBR_INTEGRATOR_PATH>, g, b, 0, ctx->stream, P, n, (const float*)in, qd, o);
-    else hipLaunchKernelGGL(k_li<PBR_INTEGRATOR_VOLPATH>, g, b, 0, ctx->stream, P, n, (const float*)in, qd, o);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(rgb_out, o, ob, hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->host.anyNoMaterial || d->sampler == PBR_SAMPLER_TABLE) {
-        HIP_TRY(hipMemcpyAsync(ctx->guardHost, ctx->dGuard.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipEventRecord(ctx->evGuard, ctx->stream));
-        ctx->guardPending = true;
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return check_guard(ctx);
+    const int rc = scratch_round_trip(ctx, n, rays, (size_t)n * 7 * 4, q, (size_t)n * 16, rgb_out, (size_t)n * 12,
+                                      [&](const char* in, const char* qIn, void* out) {
+        const dim3 g((n + 63) / 64), b(64);
+        const float* r = (const float*)in;
+        const int32_t* qd = (const int32_t*)qIn;
+        float* o = (float*)out;
+        if (d->integrator == PBR_INTEGRATOR_WHITTED) hipLaunchKernelGGL(k_li<PBR_INTEGRATOR_WHITTED>, g, b, 0, ctx->stream, P, n, r, qd, o);
+        else if (d->integrator == PBR_INTEGRATOR_PATH) hipLaunchKernelGGL(k_li<PBR_INTEGRATOR_PATH>, g, b, 0, ctx->stream, P, n, r, qd, o);
+        else hipLaunchKernelGGL(k_li<PBR_INTEGRATOR_VOLPATH>, g, b, 0, ctx->stream, P, n, r, qd, o);
+        return hand_off_guard(ctx, ctx->stream, false);   // (behind the kernel; the round trip waits for the stream)
+    });
+    return rc ? rc : check_guard(ctx);
 }
 
 int pbr_hip_set_bvh_build(pbr_hip_ctx* ctx, int where) {
@@ -2313,6 +2344,29 @@ static int frame_tiles(pbr_hip_ctx* ctx, const pbr_render_desc* d, hipStream_t s
     *nTilesOut = (int)starts.size();
     return PBR_OK;
 }
+// ... and as the tiles of a frame's kernel parameters.
+static int bind_tiles(pbr_hip_ctx* ctx, const pbr_render_desc* d, hipStream_t s, KParams* P, long long* npx) {
+    if (int rc = frame_tiles(ctx, d, s, npx, &P->nTiles)) return rc;
+    P->tiles = (const int4*)ctx->dTiles.p;
+    P->tileStart = (const long long*)ctx->dTileStart.p;
+    P->nPixels = *npx;
+    return PBR_OK;
+}
+// Per-call state of the lanes: lane 0 is the caller's stream unless this call's wf_fork moves it (a
+// call that forks nothing — the megakernel, a feature pass — must not inherit the stream an earlier
+// call chose).
+static void begin_lanes(pbr_hip_ctx* ctx, hipStream_t s) {
+    ctx->lane0 = s;
+    ctx->lastOwnLane0 = false;
+    ctx->lastPlan = wf_no_chunks();
+}
+// The call's work on `s` is a batch of one finished pass (pbr_hip_wait_frame(…, 0)).
+static int one_pass_done(pbr_hip_ctx* ctx, hipStream_t s) {
+    ctx->batchFrames = 0;
+    if (int rc = wf_frame_done(ctx, s, 0, 0u)) return rc;
+    ctx->batchFrames = 1;
+    return PBR_OK;
+}
 
 // ---- adaptive sampling (pbr_adaptive.h).  The words the host reads: ctx->dAdWords[0] the entries a
 // select left active, [1] the runs of the list last encoded, [2] set when that list was not ascending
@@ -2375,15 +2429,53 @@ static int adapt_read_words(pbr_hip_ctx* ctx, hipStream_t s, int first, int coun
     HIP_TRY(hipStreamSynchronize(s));
     return PBR_OK;
 }
-// The sampler's samplesPerPixel for d->spp (make_params: Sobol rounds up to a power of two).
-static long long sample_budget(const pbr_render_desc* d) {
-    long long spp = d->spp;
-    if (d->sampler == PBR_SAMPLER_SOBOL) {
-        long long p2 = 1;
-        while (p2 < spp) p2 <<= 1;
-        spp = p2;
-    }
-    return spp;
+
+// ---- sample passes.  The entry points that render a window of a frame's samples, in the words their
+// refusals have always used: the name, what the sample count is called, the outputs rule, and the
+// accumulator's floats per pixel.
+struct PassApi { const char *who, *samples, *outputs; int accumFloats; };
+static const char kBatchOutputs[] = "device outputs, no stats, no sample table, n >= 1";   // (every batch: render_impl)
+static const PassApi kPasses = {"render_passes", "samples_per_pass", kBatchOutputs, 6},
+                     kPassesList = {"render_passes_list", "samples", "device outputs, no stats", 6},
+                     kAdaptive = {"render_adaptive", "samples", "device outputs, no stats", 6},
+                     kAov = {"render_aov", "samples", "device outputs, no stats", 8};
+// A pass request, checked before anything is queued or any state of the context changes: n_passes passes
+// of `samples` samples from `first` onto `accum`, inside the sampler's budget (*budget).
+static int check_pass(pbr_hip_ctx* ctx, const PassApi& api, const pbr_render_desc* d, int first, int samples, int n_passes,
+                      const float* accum, long long* budget) {
+    const std::string w = std::string(api.who) + ": ";
+    if (!d) return set_err(ctx, PBR_E_INVALID, w + "null render desc");
+    if (!accum) return set_err(ctx, PBR_E_INVALID, w + "accum must be a device buffer of " + std::to_string(api.accumFloats) + " floats per pixel");
+    if (samples < 1) return set_err(ctx, PBR_E_INVALID, w + api.samples + " must be >= 1");
+    if (n_passes < 1) return set_err(ctx, PBR_E_INVALID, w + "n_passes must be >= 1");
+    if (first < 0) return set_err(ctx, PBR_E_INVALID, w + "first_sample must be >= 0");
+    if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
+    if (d->sampler == PBR_SAMPLER_TABLE) return set_err(ctx, PBR_E_UNSUPPORTED, w + "no passes over a sample table");
+    if (!d->outputs_on_device || d->collect_stats) return set_err(ctx, PBR_E_INVALID, w + api.outputs);
+    if (d->spp < 1) return set_err(ctx, PBR_E_INVALID, "spp must be positive");
+    *budget = sampler_spp(d->sampler, d->spp);
+    const long long end = (long long)first + (long long)n_passes * samples;
+    if (end > *budget)
+        return set_err(ctx, PBR_E_INVALID, w + "samples [" + std::to_string(first) + ", " + std::to_string(end) +
+                       ") run past the budget of " + std::to_string(*budget) + " samples per pixel");
+    return PBR_OK;
+}
+// The frames of a batch: n frames, or (accum) n passes of `samples` samples from `first`, or (list) one
+// pass over the nList listed pixels in the nRuns runs list_encode left.
+static FrameSet batch_frames(int n, float* const* rgb, uint8_t* const* rgba, float* accum = nullptr, int first = 0, int samples = 0,
+                             const int32_t* list = nullptr, int nList = 0, int nRuns = 0) {
+    FrameSet F;
+    F.n = n;
+    F.rgb = rgb;
+    F.rgba = rgba;
+    F.batch = true;
+    F.accum = accum;
+    F.first = first;
+    F.passSpp = samples;
+    F.list = list;
+    F.nList = nList;
+    F.nRuns = nRuns;
+    return F;
 }
 
 static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_out, uint8_t* rgba_out, pbr_render_stats* stats,
@@ -2391,9 +2483,9 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
     if (!ctx) return PBR_E_INVALID;
     if (!d) return set_err(ctx, PBR_E_INVALID, "null render desc");
     if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
+    // (a batch of passes has been through check_pass)
     if (F.batch && (!d->outputs_on_device || d->collect_stats || stats || d->sampler == PBR_SAMPLER_TABLE || F.n < 1))
-        return set_err(ctx, PBR_E_INVALID, std::string(F.accum ? "render_passes" : "render_frames") +
-                                               ": device outputs, no stats, no sample table, n >= 1");
+        return set_err(ctx, PBR_E_INVALID, std::string("render_frames: ") + kBatchOutputs);
     if (F.batch) ctx->batchFrames = 0;   // (set when the batch is queued)
     auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2406,14 +2498,10 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
         if (int rc = drain(ctx)) return rc;
     }
     if (int rc = check_guard(ctx)) return rc;
-    hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
+    hipStream_t s = call_stream(ctx, d);
     KParams P;
     if (int rc = make_params(ctx, d, &P)) return rc;
     if (F.accum) {   // sample passes: P.spp is the sampler's budget (Sobol: rounded up) until here
-        if ((long long)F.first + (long long)F.n * F.passSpp > (long long)P.spp)
-            return set_err(ctx, PBR_E_INVALID, "render_passes: samples [" + std::to_string(F.first) + ", " +
-                           std::to_string((long long)F.first + (long long)F.n * F.passSpp) + ") run past the budget of " +
-                           std::to_string(P.spp) + " samples per pixel");
         P.spp = F.passSpp;
         P.ppb = P.spp >= 256 ? 1 : 256 / P.spp;
         P.smp.passFirst = F.first;
@@ -2437,12 +2525,8 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
         }
     }
     const int spp = P.spp;
-    // tiles
     long long npx = 0;
-    if (int rc = frame_tiles(ctx, d, s, &npx, &P.nTiles)) return rc;
-    P.tiles = (const int4*)ctx->dTiles.p;
-    P.tileStart = (const long long*)ctx->dTileStart.p;
-    P.nPixels = npx;
+    if (int rc = bind_tiles(ctx, d, s, &P, &npx)) return rc;
     // A pass over a list: the listed pixels' sums are gathered into a dense accumulator, and the pass
     // renders the list's runs as tiles (list_encode) against it and dense images; list_scatter below
     // takes the results to the frame's buffers.
@@ -2484,11 +2568,7 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
     if (blocks > 0x7fffffffLL) return set_err(ctx, PBR_E_UNSUPPORTED, "frame too large");
     dim3 grid((unsigned)blocks), block(256);
     HIP_TRY(hipEventRecord(ctx->ev0, s));
-    // per-call state of the lanes: lane 0 is the caller's stream unless this call's wf_fork moves it (a
-    // call that forks nothing — the megakernel — must not inherit the stream an earlier call chose)
-    ctx->lane0 = s;
-    ctx->lastOwnLane0 = false;
-    ctx->lastPlan = wf_no_chunks();
+    begin_lanes(ctx, s);
     if (blocks > 0) {
         bool st = d->collect_stats != 0;
         // (a tree too deep for the quad walk's stack runs the megakernel's binary walk)
@@ -2535,7 +2615,7 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
             hipLaunchKernelGGL(k_adapt_scatter, dim3((F.nList + kAdaptBS - 1) / kAdaptBS), dim3(kAdaptBS), 0, s, F.list, F.nList,
                                (const float*)ctx->dListAccum.p, (const float*)denseRgb[0], (const uint32_t*)denseRgba[0],
                                F.accum, frameRgb, (uint32_t*)frameRgba);
-            if (int rc = wf_frame_done(ctx, s, 0, 0u)) return rc;
+            if (int rc = one_pass_done(ctx, s)) return rc;
         }
         HIP_TRY(hipGetLastError());
     }
@@ -2547,20 +2627,11 @@ static int render_impl(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_ou
     }
     unsigned long long hs[4] = {0, 0, 0, 0};
     if (d->collect_stats) HIP_TRY(hipMemcpyAsync(hs, ctx->dStats.p, sizeof(hs), hipMemcpyDeviceToHost, s));
-    // every frame copies the guard word out (4 B, asynchronous): a bound or a full traversal stack
-    // fails this call (synchronous frames) or the next one / pbr_hip_sync (asynchronous ones), and a
-    // bit is never left behind to fail an unrelated later frame
-    HIP_TRY(hipMemcpyAsync(ctx->guardHost, ctx->dGuard.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(ctx->evGuard, s));
-    ctx->guardPending = true;
-    if (!d->outputs_on_device || d->collect_stats || stats || d->sampler == PBR_SAMPLER_TABLE) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (int rc = check_guard(ctx)) return rc;
-    } else {
-        ctx->inFlight = true;
-        ctx->lastStream = s;
-        return PBR_OK;
-    }
+    const bool async = d->outputs_on_device && !d->collect_stats && !stats && d->sampler != PBR_SAMPLER_TABLE;
+    if (int rc = hand_off_guard(ctx, s, async)) return rc;
+    if (async) return PBR_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = check_guard(ctx)) return rc;
     auto t1 = std::chrono::steady_clock::now();
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
@@ -2586,32 +2657,15 @@ int pbr_hip_render(pbr_hip_ctx* ctx, const pbr_render_desc* d, float* rgb_out, u
 int pbr_hip_render_frames(pbr_hip_ctx* ctx, const pbr_render_desc* d, int n, float* const* rgb_outs, uint8_t* const* rgba_outs) {
     if (!ctx) return PBR_E_INVALID;
     if (n < 1) return set_err(ctx, PBR_E_INVALID, "render_frames: n must be >= 1");
-    FrameSet F;
-    F.n = n;
-    F.rgb = rgb_outs;
-    F.rgba = rgba_outs;
-    F.batch = true;
-    return render_impl(ctx, d, nullptr, nullptr, nullptr, F);
+    return render_impl(ctx, d, nullptr, nullptr, nullptr, batch_frames(n, rgb_outs, rgba_outs));
 }
 
 int pbr_hip_render_passes(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sample, int samples_per_pass, int n_passes,
                           float* accum, float* const* rgb_outs, uint8_t* const* rgba_outs) {
     if (!ctx) return PBR_E_INVALID;
-    if (!d) return set_err(ctx, PBR_E_INVALID, "render_passes: null render desc");
-    if (!accum) return set_err(ctx, PBR_E_INVALID, "render_passes: accum must be a device buffer of 6 floats per pixel");
-    if (samples_per_pass < 1) return set_err(ctx, PBR_E_INVALID, "render_passes: samples_per_pass must be >= 1");
-    if (n_passes < 1) return set_err(ctx, PBR_E_INVALID, "render_passes: n_passes must be >= 1");
-    if (first_sample < 0) return set_err(ctx, PBR_E_INVALID, "render_passes: first_sample must be >= 0");
-    if (d->sampler == PBR_SAMPLER_TABLE) return set_err(ctx, PBR_E_UNSUPPORTED, "render_passes: no passes over a sample table");
-    FrameSet F;
-    F.n = n_passes;
-    F.rgb = rgb_outs;
-    F.rgba = rgba_outs;
-    F.batch = true;
-    F.accum = accum;
-    F.first = first_sample;
-    F.passSpp = samples_per_pass;
-    return render_impl(ctx, d, nullptr, nullptr, nullptr, F);
+    long long budget = 0;
+    if (int rc = check_pass(ctx, kPasses, d, first_sample, samples_per_pass, n_passes, accum, &budget)) return rc;
+    return render_impl(ctx, d, nullptr, nullptr, nullptr, batch_frames(n_passes, rgb_outs, rgba_outs, accum, first_sample, samples_per_pass));
 }
 
 int pbr_hip_adaptive_select(pbr_hip_ctx* ctx, int64_t n_pixels, int samples_done, float tolerance, float floor, const float* accum,
@@ -2631,80 +2685,41 @@ int pbr_hip_adaptive_select(pbr_hip_ctx* ctx, int64_t n_pixels, int samples_done
     return adapt_read_words(ctx, ctx->stream, 0, 1, n_out);
 }
 
-// What the listed-pass entry points share with pbr_hip_render_passes, checked before anything is queued.
-static int list_pass_check(pbr_hip_ctx* ctx, const pbr_render_desc* d, const char* who, long long* budget) {
-    const std::string w(who);
-    if (!d) return set_err(ctx, PBR_E_INVALID, w + ": null render desc");
-    if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
-    if (d->sampler == PBR_SAMPLER_TABLE) return set_err(ctx, PBR_E_UNSUPPORTED, w + ": no passes over a sample table");
-    if (!d->outputs_on_device || d->collect_stats) return set_err(ctx, PBR_E_INVALID, w + ": device outputs, no stats");
-    if (d->spp < 1) return set_err(ctx, PBR_E_INVALID, "spp must be positive");
-    *budget = sample_budget(d);
-    return PBR_OK;
-}
-static FrameSet list_frame_set(int first, int samples, const int32_t* list, int nList, int nRuns, float* accum, float* const* rgb,
-                               uint8_t* const* rgba) {
-    FrameSet F;
-    F.n = 1;
-    F.rgb = rgb;
-    F.rgba = rgba;
-    F.batch = true;
-    F.accum = accum;
-    F.first = first;
-    F.passSpp = samples;
-    F.list = list;
-    F.nList = nList;
-    F.nRuns = nRuns;
-    return F;
-}
-
 int pbr_hip_render_passes_list(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sample, int samples, const int32_t* list,
                                int n_list, float* accum, float* rgb_out, uint8_t* rgba_out) {
     if (!ctx) return PBR_E_INVALID;
     long long budget = 0;
-    if (int rc = list_pass_check(ctx, d, "render_passes_list", &budget)) return rc;
-    if (!accum) return set_err(ctx, PBR_E_INVALID, "render_passes_list: accum must be a device buffer of 6 floats per pixel");
-    if (samples < 1) return set_err(ctx, PBR_E_INVALID, "render_passes_list: samples must be >= 1");
-    if (first_sample < 0) return set_err(ctx, PBR_E_INVALID, "render_passes_list: first_sample must be >= 0");
-    if ((long long)first_sample + samples > budget)
-        return set_err(ctx, PBR_E_INVALID, "render_passes_list: samples [" + std::to_string(first_sample) + ", " +
-                       std::to_string((long long)first_sample + samples) + ") run past the budget of " + std::to_string(budget) +
-                       " samples per pixel");
+    if (int rc = check_pass(ctx, kPassesList, d, first_sample, samples, 1, accum, &budget)) return rc;
     if (n_list < 0 || (n_list > 0 && !list)) return set_err(ctx, PBR_E_INVALID, "render_passes_list: n_list >= 0 and a list");
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
+    hipStream_t s = call_stream(ctx, d);
     long long npx = 0;
     int nTiles = 0;
     if (int rc = frame_tiles(ctx, d, s, &npx, &nTiles)) return rc;
     if (npx >= (1ll << 31)) return set_err(ctx, PBR_E_UNSUPPORTED, "render_passes_list: pixel indices beyond int32");
     if ((long long)n_list > npx) return set_err(ctx, PBR_E_INVALID, "render_passes_list: more listed pixels than the tiles hold");
-    if (n_list == 0) {   // nothing to render: an empty batch of one finished pass
-        ctx->batchFrames = 0;
-        if (int rc = wf_frame_done(ctx, s, 0, 0u)) return rc;
-        ctx->batchFrames = 1;
-        return PBR_OK;
-    }
+    if (n_list == 0) return one_pass_done(ctx, s);   // nothing to render: an empty batch of one finished pass
     if (int rc = list_encode(ctx, s, list, n_list, false, npx, nTiles)) return rc;
     int w[2] = {0, 0};   // runs, bad list
     if (int rc = adapt_read_words(ctx, s, 1, 2, w)) return rc;
     if (w[1]) return set_err(ctx, PBR_E_INVALID, "render_passes_list: the list must hold ascending packed pixel indices of the tiles");
     float* rgb[1] = {rgb_out};
     uint8_t* rgba[1] = {rgba_out};
-    return render_impl(ctx, d, nullptr, nullptr, nullptr, list_frame_set(first_sample, samples, list, n_list, w[0], accum, rgb, rgba));
+    return render_impl(ctx, d, nullptr, nullptr, nullptr, batch_frames(1, rgb, rgba, accum, first_sample, samples, list, n_list, w[0]));
 }
 
 int pbr_hip_render_adaptive(pbr_hip_ctx* ctx, const pbr_render_desc* d, const pbr_adaptive* a, float* accum, int32_t* counts,
                             float* rgb_out, uint8_t* rgba_out, pbr_adaptive_result* result) {
     if (!ctx) return PBR_E_INVALID;
-    long long budget = 0;
-    if (int rc = list_pass_check(ctx, d, "render_adaptive", &budget)) return rc;
     if (!a || !accum || !counts) return set_err(ctx, PBR_E_INVALID, "render_adaptive: parameters, accum and counts are required");
+    long long budget = 0;   // (its own words for the window: min_samples in the budget, below)
+    if (int rc = check_pass(ctx, kAdaptive, d, 0, 1, 1, accum, &budget)) return rc;
     if (a->min_samples < 2 || a->min_samples > budget)
         return set_err(ctx, PBR_E_INVALID, "render_adaptive: min_samples must be in [2, " + std::to_string(budget) + "] (the budget)");
     if (a->samples_per_round < 1) return set_err(ctx, PBR_E_INVALID, "render_adaptive: samples_per_round must be >= 1");
     if (!(a->tolerance >= 0.f) || !(a->floor >= 0.f)) return set_err(ctx, PBR_E_INVALID, "render_adaptive: tolerance and floor must be >= 0");
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
+    hipStream_t s = call_stream(ctx, d);
     long long npx = 0;
     int nTiles = 0;
     if (int rc = frame_tiles(ctx, d, s, &npx, &nTiles)) return rc;
@@ -2733,7 +2748,7 @@ int pbr_hip_render_adaptive(pbr_hip_ctx* ctx, const pbr_render_desc* d, const pb
         R.active_at_end = w[0];
         if (!more || w[0] == 0) break;
         const int step = (int)std::min<long long>(a->samples_per_round, budget - k);
-        if (int rc = render_impl(ctx, d, nullptr, nullptr, nullptr, list_frame_set(k, step, next, w[0], w[1], accum, rgb, rgba))) return rc;
+        if (int rc = render_impl(ctx, d, nullptr, nullptr, nullptr, batch_frames(1, rgb, rgba, accum, k, step, next, w[0], w[1]))) return rc;
         k += step;
         hipLaunchKernelGGL(k_adapt_counts, dim3((w[0] + kAdaptBS - 1) / kAdaptBS), blk, 0, s, (const int32_t*)next, w[0], counts, k);
         list = next;
@@ -2764,13 +2779,8 @@ int pbr_hip_plan_aov(int64_t n_pixels, int samples, int max_launches, int64_t* f
 
 int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sample, int samples, float* accum, float* aov_out) {
     if (!ctx) return PBR_E_INVALID;
-    if (!d) return set_err(ctx, PBR_E_INVALID, "render_aov: null render desc");
-    if (!accum) return set_err(ctx, PBR_E_INVALID, "render_aov: accum must be a device buffer of 8 floats per pixel");
-    if (samples < 1) return set_err(ctx, PBR_E_INVALID, "render_aov: samples must be >= 1");
-    if (first_sample < 0) return set_err(ctx, PBR_E_INVALID, "render_aov: first_sample must be >= 0");
-    if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
-    if (d->sampler == PBR_SAMPLER_TABLE) return set_err(ctx, PBR_E_UNSUPPORTED, "render_aov: no passes over a sample table");
-    if (!d->outputs_on_device || d->collect_stats) return set_err(ctx, PBR_E_INVALID, "render_aov: device outputs, no stats");
+    long long budget = 0;
+    if (int rc = check_pass(ctx, kAov, d, first_sample, samples, 1, accum, &budget)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     // as a render: a scene with material-less primitives can trip the crossing bound, so its earlier
     // asynchronous frame is waited for and checked; every other call stays queued back to back
@@ -2778,7 +2788,7 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
         if (int rc = drain(ctx)) return rc;
     }
     if (int rc = check_guard(ctx)) return rc;
-    hipStream_t s = d->stream ? (hipStream_t)d->stream : ctx->stream;
+    hipStream_t s = call_stream(ctx, d);
     // the camera, sampler, spp and tiles of the descriptor; its integrator, depth, roulette and light
     // strategy are not read (make_params validates them, so they are set to values that always pass)
     pbr_render_desc dd = *d;
@@ -2789,27 +2799,18 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
     std::memset(&A, 0, sizeof(A));
     if (int rc = make_params(ctx, &dd, &A.P)) return rc;
     KParams& P = A.P;   // (P.spp is the sampler's budget until here)
-    if ((long long)first_sample + samples > (long long)P.spp)
-        return set_err(ctx, PBR_E_INVALID, "render_aov: samples [" + std::to_string(first_sample) + ", " +
-                       std::to_string((long long)first_sample + samples) + ") run past the budget of " + std::to_string(P.spp) +
-                       " samples per pixel");
     P.spp = samples;
     P.ppb = aov_pixels_per_block(samples);
     P.smp.passFirst = first_sample;
     long long npx = 0;
-    if (int rc = frame_tiles(ctx, d, s, &npx, &P.nTiles)) return rc;   // (another stream: drains the context first)
-    P.tiles = (const int4*)ctx->dTiles.p;
-    P.tileStart = (const long long*)ctx->dTileStart.p;
-    P.nPixels = npx;
+    if (int rc = bind_tiles(ctx, d, s, &P, &npx)) return rc;   // (another stream: drains the context first)
     A.accum = accum;
     A.out = aov_out;
     A.albedo = (const float4*)ctx->dAlbedo.p;
     const bool tex = !ctx->host.texMats.empty(), binary = P.S.binaryWalk != 0;
     const int kind = tex ? KP_AOV_TEX : KP_AOV;
     ctx->batchFrames = 0;   // (set when the pass is queued)
-    ctx->lane0 = s;
-    ctx->lastOwnLane0 = false;
-    ctx->lastPlan = wf_no_chunks();
+    begin_lanes(ctx, s);
     for (const AovLaunch& l : aov_launches(npx, samples)) {
         A.pix0 = l.pix0;
         A.pixEnd = l.pix0 + l.nPix;
@@ -2823,15 +2824,8 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
     prof_host(ctx, kind, 1, (unsigned long long)npx);
     if (first_sample > 0) prof_host(ctx, kind, 2, (unsigned long long)npx);
     if (aov_out) prof_host(ctx, kind, 3, (unsigned long long)npx);
-    if (int rc = wf_frame_done(ctx, s, 0, 0u)) return rc;
-    ctx->batchFrames = 1;
-    // the guard word, as at the end of every frame (render_impl)
-    HIP_TRY(hipMemcpyAsync(ctx->guardHost, ctx->dGuard.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(ctx->evGuard, s));
-    ctx->guardPending = true;
-    ctx->inFlight = true;
-    ctx->lastStream = s;
-    return PBR_OK;
+    if (int rc = one_pass_done(ctx, s)) return rc;
+    return hand_off_guard(ctx, s, true);
 }
 
 int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f) {
@@ -3037,15 +3031,10 @@ int pbr_hip_sampler_values(pbr_hip_ctx* ctx, int sampler, int width, int height,
         if (q[4 * i] < 0 || q[4 * i + 1] < 0 || q[4 * i + 2] < 0 || q[4 * i + 3] < 0 || q[4 * i + 3] >= maxDims)
             return set_err(ctx, PBR_E_INVALID, "sampler query: negative pixel / sample or dimension beyond the tables");
     HaltonParams hp = hparams(s);
-    HIP_TRY(ctx->dScratchIn.ensure((size_t)n * 16));
-    HIP_TRY(ctx->dScratchOut.ensure((size_t)n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->dScratchIn.p, q, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (n > 0) hipLaunchKernelGGL(k_sampler_values, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s, hp, n,
-                                  (const int32_t*)ctx->dScratchIn.p, (float*)ctx->dScratchOut.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PBR_OK;
+    return scratch_round_trip(ctx, n, q, (size_t)n * 16, nullptr, 0, out, (size_t)n * 4, [&](const char* in, const char*, void* o) {
+        hipLaunchKernelGGL(k_sampler_values, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s, hp, n, (const int32_t*)in, (float*)o);
+        return PBR_OK;
+    });
 }
 
 // The device samplers as queried by the host API's GlobalSampler (include/pbr/pbr.h): the
@@ -3056,9 +3045,7 @@ static int query_sampler(pbr_hip_ctx* ctx, int sampler, int width, int height, i
     *s = device_sampler(ctx, sampler, spp, width, height);
     if (sampler == PBR_SAMPLER_SOBOL) {
         if (int rc = prepare_sobol(ctx, nullptr, 0, width, height, s)) return rc;
-        int p2 = 1;
-        while (p2 < spp) p2 <<= 1;
-        s->spp = p2;
+        s->spp = (int)sampler_spp(sampler, spp);
     }
     return PBR_OK;
 }
@@ -3072,15 +3059,10 @@ int pbr_hip_sample_index(pbr_hip_ctx* ctx, int sampler, int width, int height, i
     for (int i = 0; i < n; ++i)
         if (q[3 * i] < 0 || q[3 * i + 1] < 0 || q[3 * i + 2] < 0) return set_err(ctx, PBR_E_INVALID, "sample_index: negative pixel or sample");
     if (n == 0) return PBR_OK;
-    HIP_TRY(ctx->dScratchIn.ensure((size_t)n * 12));
-    HIP_TRY(ctx->dScratchOut.ensure((size_t)n * 8));
-    HIP_TRY(hipMemcpyAsync(ctx->dScratchIn.p, q, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_sample_index, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s, n, (const int32_t*)ctx->dScratchIn.p,
-                       (long long*)ctx->dScratchOut.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PBR_OK;
+    return scratch_round_trip(ctx, n, q, (size_t)n * 12, nullptr, 0, out, (size_t)n * 8, [&](const char* in, const char*, void* o) {
+        hipLaunchKernelGGL(k_sample_index, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s, n, (const int32_t*)in, (long long*)o);
+        return PBR_OK;
+    });
 }
 
 int pbr_hip_sample_dimensions(pbr_hip_ctx* ctx, int sampler, int width, int height, int n, const int64_t* index, const int32_t* q,
@@ -3098,17 +3080,12 @@ int pbr_hip_sample_dimensions(pbr_hip_ctx* ctx, int sampler, int width, int heig
             return set_err(ctx, PBR_E_INVALID, "sample_dimensions: index out of range");
     }
     if (n == 0) return PBR_OK;
-    HIP_TRY(ctx->dScratchIn.ensure((size_t)n * 20));
-    HIP_TRY(ctx->dScratchOut.ensure((size_t)n * 4));
-    char* in = (char*)ctx->dScratchIn.p;
-    HIP_TRY(hipMemcpyAsync(in, index, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(in + (size_t)n * 8, q, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_sample_dimensions, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s, n, (const long long*)in,
-                       (const int32_t*)(in + (size_t)n * 8), (float*)ctx->dScratchOut.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PBR_OK;
+    return scratch_round_trip(ctx, n, index, (size_t)n * 8, q, (size_t)n * 12, out, (size_t)n * 4,
+                              [&](const char* idx, const char* qIn, void* o) {
+        hipLaunchKernelGGL(k_sample_dimensions, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, s, n, (const long long*)idx,
+                           (const int32_t*)qIn, (float*)o);
+        return PBR_OK;
+    });
 }
 
 int pbr_hip_camera_rays(pbr_hip_ctx* ctx, const pbr_camera_desc* cam, int n, const float* pf, float* out) {
@@ -3120,32 +3097,21 @@ int pbr_hip_camera_rays(pbr_hip_ctx* ctx, const pbr_camera_desc* cam, int n, con
     } catch (const std::exception& e) {
         return set_err(ctx, PBR_E_INVALID, e.what());
     }
-    HIP_TRY(ctx->dScratchIn.ensure((size_t)n * 8));
-    HIP_TRY(ctx->dScratchOut.ensure((size_t)n * 24));
-    HIP_TRY(hipMemcpyAsync(ctx->dScratchIn.p, pf, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (n > 0) hipLaunchKernelGGL(k_camera_rays, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dc, n,
-                                  (const float*)ctx->dScratchIn.p, (float*)ctx->dScratchOut.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PBR_OK;
+    return scratch_round_trip(ctx, n, pf, (size_t)n * 8, nullptr, 0, out, (size_t)n * 24, [&](const char* in, const char*, void* o) {
+        hipLaunchKernelGGL(k_camera_rays, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, dc, n, (const float*)in, (float*)o);
+        return PBR_OK;
+    });
 }
 
 int pbr_hip_intersect(pbr_hip_ctx* ctx, int n, const float* rays, float* out, int any_hit) {
     if (!ctx || !rays || !out || n < 0) return PBR_E_INVALID;
     if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->dScratchIn.ensure((size_t)n * 28));
-    HIP_TRY(ctx->dScratchOut.ensure((size_t)n * 20));
-    HIP_TRY(hipMemcpyAsync(ctx->dScratchIn.p, rays, (size_t)n * 28, hipMemcpyHostToDevice, ctx->stream));
-    DeviceScene S = device_scene(ctx);
-    if (n > 0) hipLaunchKernelGGL(k_intersect, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, S,
-                                  (const int32_t*)ctx->dPrimIds.p, n, (const float*)ctx->dScratchIn.p,
-                                  (float*)ctx->dScratchOut.p, any_hit);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ctx->dScratchOut.p, (size_t)n * 20, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return PBR_OK;
+    return scratch_round_trip(ctx, n, rays, (size_t)n * 28, nullptr, 0, out, (size_t)n * 20, [&](const char* in, const char*, void* o) {
+        hipLaunchKernelGGL(k_intersect, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, device_scene(ctx),
+                           (const int32_t*)ctx->dPrimIds.p, n, (const float*)in, (float*)o, any_hit);
+        return PBR_OK;
+    });
 }
 
 int pbr_hip_intersect_walk(pbr_hip_ctx* ctx, int walk, int n, const float* rays, float* out, int any_hit, int seg_cap,
@@ -3251,9 +3217,7 @@ int pbr_hip_intersect_walk(pbr_hip_ctx* ctx, int walk, int n, const float* rays,
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(out, dOut, (size_t)n * 20, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(ctx->guardHost, ctx->dGuard.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(ctx->evGuard, st));
-    ctx->guardPending = true;
+    if (int rc = hand_off_guard(ctx, st, false)) return rc;
     HIP_TRY(hipStreamSynchronize(st));   // (the scratch queue is freed after this)
     return check_guard(ctx);
 }

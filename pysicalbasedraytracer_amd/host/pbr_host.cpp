@@ -1167,35 +1167,67 @@ pbr_hip_ctx* helper_ctx() {
     if (!h) check(nullptr, pbr_hip_create(0, &h), "pbr_hip_create");
     return h;
 }
+// A packed image (tile after tile, as rendered) into the FrameBuffer, when there is one.
+void write_framebuffer(FrameBuffer* fb, const std::string& who, const std::vector<pbr_tile>& tl, const float* rgb,
+                       const uint8_t* rgba, int W, int H) {
+    if (!fb) return;
+    if (fb->width != W || fb->height != H || fb->channals < 3)
+        throw std::invalid_argument(who + ": FrameBuffer not initialised to the pixel bounds");
+    size_t k = 0;
+    for (const pbr_tile& t : tl)
+        for (int y = t.y0; y < t.y1; ++y)
+            for (int x = t.x0; x < t.x1; ++x, ++k)
+                for (int ch = 0; ch < fb->channals; ++ch) {
+                    // Integrator.cpp:341-344: set_uc(x, pMax.y - y - 1, ...) — the image is flipped
+                    fb->set_uc(x, H - y - 1, ch, rgba[4 * k + ch]);
+                    fb->set_fc(x, H - y - 1, ch, ch < 3 ? rgb[3 * k + ch] : 1.f);
+                }
+}
 }  // namespace
+
+// What every render entry point asks the device for.  The checks they share (`who` names the caller in
+// the refusals), then the render descriptor from the integrator's fields, the tiles (SetTiles, else the
+// pixel bounds) and their pixel count.  Touches no device.
+struct SamplerIntegrator::FrameRequest {
+    const PerspectiveCamera* cam;
+    const int W, H;   // the reference reads pMax only
+    std::shared_ptr<FlatScene> flat;
+    pbr_render_desc rd;
+    std::vector<pbr_tile> tl;
+    size_t npx = 0;
+    FrameRequest(const FrameRequest&) = delete;   // (rd.tiles points into tl)
+    FrameRequest(const SamplerIntegrator& in, const Scene& scene, const std::string& who)
+        : cam(dynamic_cast<const PerspectiveCamera*>(in.camera.get())), W(in.pixelBounds.pMax.x), H(in.pixelBounds.pMax.y) {
+        if (!cam) throw std::invalid_argument(who + ": only PerspectiveCamera is on the GPU path");
+        check_sampler(*in.sampler, *cam, who.c_str());
+        if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
+            throw std::invalid_argument(who + ": pixelBounds outside the camera raster");
+        flat = FlattenScene(scene, cam->medium);   // for the camera medium's index
+        std::memset(&rd, 0, sizeof(rd));
+        rd.integrator = in.IntegratorType();
+        rd.max_depth = in.MaxDepth();
+        rd.rr_threshold = in.RRThreshold();
+        rd.light_strategy = in.LightStrategy();
+        rd.sampler = in.sampler->DeviceSampler();
+        rd.spp = (int)in.sampler->samplesPerPixel;
+        camera_desc(*cam, &rd.camera);
+        rd.camera.medium = MediumIndex(*flat, cam->medium);
+        for (const Bounds2i& b : in.tiles) tl.push_back({b.pMin.x, b.pMin.y, b.pMax.x, b.pMax.y});
+        if (tl.empty()) tl.push_back({0, 0, W, H});
+        rd.n_tiles = (int)tl.size();
+        rd.tiles = tl.data();
+        for (const pbr_tile& t : tl) npx += (size_t)(t.x1 - t.x0) * (t.y1 - t.y0);
+    }
+};
 
 void SamplerIntegrator::Render(const Scene& scene, double& timeConsume) {
     if (!devices.empty()) return RenderMulti(scene, timeConsume);
     auto t0 = std::chrono::steady_clock::now();
-    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
-    if (!cam) throw std::invalid_argument("Render: only PerspectiveCamera is on the GPU path");
-    check_sampler(*sampler, *cam, "Render");
-    const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;   // the reference reads pMax only
-    if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
-        throw std::invalid_argument("Render: pixelBounds outside the camera raster");
+    FrameRequest q(*this, scene, "Render");
     ensure_scene(scene);
-    auto flat = FlattenScene(scene, cam->medium);   // for the camera medium's index
-    pbr_render_desc rd;
-    std::memset(&rd, 0, sizeof(rd));
-    rd.integrator = IntegratorType();
-    rd.max_depth = MaxDepth();
-    rd.rr_threshold = RRThreshold();
-    rd.light_strategy = LightStrategy();
-    rd.sampler = sampler->DeviceSampler();
-    rd.spp = (int)sampler->samplesPerPixel;
-    camera_desc(*cam, &rd.camera);
-    rd.camera.medium = MediumIndex(*flat, cam->medium);
-    std::vector<pbr_tile> tl;
-    if (!tiles.empty()) {
-        for (const Bounds2i& b : tiles) tl.push_back({b.pMin.x, b.pMin.y, b.pMax.x, b.pMax.y});
-    } else {
-        tl.push_back({0, 0, W, H});
-    }
+    const PerspectiveCamera* cam = q.cam;
+    pbr_render_desc& rd = q.rd;
+    const std::vector<pbr_tile>& tl = q.tl;
     std::vector<float> table;
     // A GlobalSampler the device cannot compute: its values for every pixel and sample of the frame,
     // taken the way Render's loop takes them (Integrator.cpp:290-300: Clone(offset), StartPixel, then
@@ -1238,12 +1270,8 @@ void SamplerIntegrator::Render(const Scene& scene, double& timeConsume) {
                                                          : 5 + (depth + 1) * 10 + 2;
         tabulate(dims);
     }
-    rd.n_tiles = (int)tl.size();
-    rd.tiles = tl.data();
-    size_t npx = 0;
-    for (const pbr_tile& t : tl) npx += (size_t)(t.x1 - t.x0) * (t.y1 - t.y0);
-    std::vector<float> rgb(npx * 3);
-    std::vector<uint8_t> rgba(npx * 4);
+    std::vector<float> rgb(q.npx * 3);
+    std::vector<uint8_t> rgba(q.npx * 4);
     pbr_render_stats st;
     // Retry only when the sample-table bound is the ONE guard bit the frame tripped (check_guard lists
     // the bits in a fixed order and the sample table's comes last, so its clause then opens the
@@ -1267,19 +1295,7 @@ void SamplerIntegrator::Render(const Scene& scene, double& timeConsume) {
         check(ctx, rc, "pbr_hip_render");
         break;
     }
-    if (m_FrameBuffer) {
-        if (m_FrameBuffer->width != W || m_FrameBuffer->height != H || m_FrameBuffer->channals < 3)
-            throw std::invalid_argument("Render: FrameBuffer not initialised to the pixel bounds");
-        size_t k = 0;
-        for (const pbr_tile& t : tl)
-            for (int y = t.y0; y < t.y1; ++y)
-                for (int x = t.x0; x < t.x1; ++x, ++k)
-                    for (int ch = 0; ch < m_FrameBuffer->channals; ++ch) {
-                        // Integrator.cpp:341-344: set_uc(x, pMax.y - y - 1, ...) — the image is flipped
-                        m_FrameBuffer->set_uc(x, H - y - 1, ch, rgba[4 * k + ch]);
-                        m_FrameBuffer->set_fc(x, H - y - 1, ch, ch < 3 ? rgb[3 * k + ch] : 1.f);
-                    }
-    }
+    write_framebuffer(m_FrameBuffer, "Render", tl, rgb.data(), rgba.data(), q.W, q.H);
     stats.seconds = st.seconds;
     stats.kernel_ms = st.kernel_ms;
     stats.samples = st.samples;
@@ -1548,18 +1564,38 @@ void AssembleTiles(const std::vector<Bounds2i>& tiles, const float* packed, int 
     assemble(tiles, packed, ch, width, frame);
 }
 
-// Device buffers of RenderSamples: 6 floats of sums, 3 floats and 4 bytes of image per pixel.
-struct SamplerIntegrator::Progressive {
+// The device buffers sample passes carry from call to call.  RenderSamples: 6 floats of sums, 3 floats and
+// 4 bytes of image per pixel; RenderFeatures: 8 floats of sums and 8 floats of image per pixel.
+struct SamplerIntegrator::PassBuffers {
     int device = 0;
     size_t npx = 0;
-    float* accum = nullptr;
-    float* rgb = nullptr;
-    uint8_t* rgba = nullptr;
-    ~Progressive() {
+    std::vector<void*> p;
+    ~PassBuffers() {
         if (hipSetDevice(device) != hipSuccess) return;
-        if (accum) (void)hipFree(accum);
-        if (rgb) (void)hipFree(rgb);
-        if (rgba) (void)hipFree(rgba);
+        for (void* q : p) (void)hipFree(q);
+    }
+    // Continue the passes held in `h` (`done` samples so far) at firstSample, or start over at 0: refuses
+    // what cannot continue, makes sure of the context and the scene, and allocates the buffers — these
+    // bytes per pixel each — when there are none or the pixel count or the device changed.
+    static void continue_at(std::shared_ptr<PassBuffers>& h, const SamplerIntegrator& in, const Scene& scene, const std::string& who,
+                            int firstSample, int done, size_t npx, std::initializer_list<size_t> bytesPerPixel) {
+        if (in.sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
+            throw std::invalid_argument(who + ": a custom sampler's values go to the device as a whole frame's table; "
+                                        "sample passes need HaltonSampler or SobolSampler");
+        if (firstSample != 0 && (!h || firstSample != done))
+            throw std::invalid_argument(who + ": firstSample " + std::to_string(firstSample) + " does not continue the " +
+                                        std::to_string(h ? done : 0) + " samples done");
+        in.ensure_scene(scene);
+        hip_check(hipSetDevice(in.device), "hipSetDevice");
+        if (h && h->npx == npx && h->device == in.device) return;
+        if (firstSample != 0) throw std::invalid_argument(who + ": the tiles changed since the last call");
+        h = std::make_shared<PassBuffers>();
+        h->device = in.device;
+        h->npx = npx;
+        for (size_t b : bytesPerPixel) {
+            h->p.push_back(nullptr);
+            hip_check(hipMalloc(&h->p.back(), std::max<size_t>(1, npx) * b), "hipMalloc");
+        }
     }
 };
 
@@ -1580,73 +1616,23 @@ std::vector<int> SamplerIntegrator::RenderAdaptive(const Scene& scene, int minSa
     return RenderPass(scene, "RenderAdaptive", 0, 0, &a);
 }
 
-// Device buffers of RenderFeatures: 8 floats of sums and 8 floats of image per pixel.
-struct SamplerIntegrator::Features {
-    int device = 0;
-    size_t npx = 0;
-    float* accum = nullptr;
-    float* image = nullptr;
-    ~Features() {
-        if (hipSetDevice(device) != hipSuccess) return;
-        if (accum) (void)hipFree(accum);
-        if (image) (void)hipFree(image);
-    }
-};
-
 void SamplerIntegrator::RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out) {
     const std::string who("RenderFeatures");
     if (firstSample < 0 || nSamples < 1) throw std::invalid_argument(who + ": firstSample >= 0 and nSamples >= 1");
     if (!out) throw std::invalid_argument(who + ": out == nullptr");
     if (!devices.empty()) throw std::invalid_argument(who + ": one device (SetDevice), not SetDevices");
-    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
-    if (!cam) throw std::invalid_argument(who + ": only PerspectiveCamera is on the GPU path");
-    check_sampler(*sampler, *cam, "RenderFeatures");
-    if (sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
-        throw std::invalid_argument(who + ": a custom sampler's values go to the device as a whole frame's table; "
-                                    "sample passes need HaltonSampler or SobolSampler");
-    if (firstSample != 0 && (!feat || firstSample != featuresDone))
-        throw std::invalid_argument(who + ": firstSample " + std::to_string(firstSample) + " does not continue the " +
-                                    std::to_string(feat ? featuresDone : 0) + " samples done");
-    const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;   // the reference reads pMax only
-    if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
-        throw std::invalid_argument(who + ": pixelBounds outside the camera raster");
-    ensure_scene(scene);
-    auto flat = FlattenScene(scene, cam->medium);   // for the camera medium's index
-    pbr_render_desc rd;
-    std::memset(&rd, 0, sizeof(rd));
-    rd.integrator = IntegratorType();   // (not read by a feature pass)
-    rd.max_depth = MaxDepth();
-    rd.rr_threshold = RRThreshold();
-    rd.light_strategy = LightStrategy();
-    rd.sampler = sampler->DeviceSampler();
-    rd.spp = (int)sampler->samplesPerPixel;
-    camera_desc(*cam, &rd.camera);
-    rd.camera.medium = MediumIndex(*flat, cam->medium);
-    std::vector<pbr_tile> tl;
-    if (!tiles.empty()) {
-        for (const Bounds2i& b : tiles) tl.push_back({b.pMin.x, b.pMin.y, b.pMax.x, b.pMax.y});
-    } else {
-        tl.push_back({0, 0, W, H});
-    }
-    rd.n_tiles = (int)tl.size();
-    rd.tiles = tl.data();
-    rd.outputs_on_device = 1;
-    size_t npx = 0;
-    for (const pbr_tile& t : tl) npx += (size_t)(t.x1 - t.x0) * (t.y1 - t.y0);
-    hip_check(hipSetDevice(device), "hipSetDevice");
-    if (!feat || feat->npx != npx || feat->device != device) {
-        if (firstSample != 0) throw std::invalid_argument(who + ": the tiles changed since the last call");
-        feat = std::make_shared<Features>();
-        feat->device = device;
-        feat->npx = npx;
-        hip_check(hipMalloc((void**)&feat->accum, std::max<size_t>(1, npx) * PBR_AOV_CHANNELS * sizeof(float)), "hipMalloc");
-        hip_check(hipMalloc((void**)&feat->image, std::max<size_t>(1, npx) * PBR_AOV_CHANNELS * sizeof(float)), "hipMalloc");
-    }
-    check(ctx, pbr_hip_render_aov(ctx, &rd, firstSample, nSamples, feat->accum, feat->image), "pbr_hip_render_aov");
+    FrameRequest q(*this, scene, who);   // (its integrator, depth and light strategy are not read by a feature pass)
+    q.rd.outputs_on_device = 1;
+    const size_t px = PBR_AOV_CHANNELS * sizeof(float);
+    PassBuffers::continue_at(feat, *this, scene, who, firstSample, featuresDone, q.npx, {px, px});
+    float *accum = (float*)feat->p[0], *image = (float*)feat->p[1];
+    check(ctx, pbr_hip_render_aov(ctx, &q.rd, firstSample, nSamples, accum, image), "pbr_hip_render_aov");
     check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
     featuresDone = firstSample + nSamples;
-    std::vector<float> img(npx * PBR_AOV_CHANNELS);
-    hip_check(hipMemcpy(img.data(), feat->image, img.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+    const int W = q.W, H = q.H;
+    const std::vector<pbr_tile>& tl = q.tl;
+    std::vector<float> img(q.npx * PBR_AOV_CHANNELS);
+    hip_check(hipMemcpy(img.data(), image, img.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
     out->width = W;
     out->height = H;
     out->albedo.assign((size_t)W * H * 3, 0.f);
@@ -1672,61 +1658,23 @@ std::vector<int> SamplerIntegrator::RenderPass(const Scene& scene, const char* w
                                                const pbr_adaptive* adaptive) {
     const std::string who(whoName);
     if (!devices.empty()) throw std::invalid_argument(who + ": one device (SetDevice), not SetDevices");
-    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
-    if (!cam) throw std::invalid_argument(who + ": only PerspectiveCamera is on the GPU path");
-    check_sampler(*sampler, *cam, whoName);
-    if (sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
-        throw std::invalid_argument(who + ": a custom sampler's values go to the device as a whole frame's table; "
-                                    "sample passes need HaltonSampler or SobolSampler");
-    if (firstSample != 0 && (!prog || firstSample != samplesDone))
-        throw std::invalid_argument(who + ": firstSample " + std::to_string(firstSample) + " does not continue the " +
-                                    std::to_string(prog ? samplesDone : 0) + " samples done");
-    const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;   // the reference reads pMax only
-    if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
-        throw std::invalid_argument(who + ": pixelBounds outside the camera raster");
-    ensure_scene(scene);
-    auto flat = FlattenScene(scene, cam->medium);   // for the camera medium's index
-    pbr_render_desc rd;
-    std::memset(&rd, 0, sizeof(rd));
-    rd.integrator = IntegratorType();
-    rd.max_depth = MaxDepth();
-    rd.rr_threshold = RRThreshold();
-    rd.light_strategy = LightStrategy();
-    rd.sampler = sampler->DeviceSampler();
-    rd.spp = (int)sampler->samplesPerPixel;
-    camera_desc(*cam, &rd.camera);
-    rd.camera.medium = MediumIndex(*flat, cam->medium);
-    std::vector<pbr_tile> tl;
-    if (!tiles.empty()) {
-        for (const Bounds2i& b : tiles) tl.push_back({b.pMin.x, b.pMin.y, b.pMax.x, b.pMax.y});
-    } else {
-        tl.push_back({0, 0, W, H});
-    }
-    rd.n_tiles = (int)tl.size();
-    rd.tiles = tl.data();
+    FrameRequest q(*this, scene, who);
+    pbr_render_desc& rd = q.rd;
     rd.outputs_on_device = 1;
-    size_t npx = 0;
-    for (const pbr_tile& t : tl) npx += (size_t)(t.x1 - t.x0) * (t.y1 - t.y0);
-    hip_check(hipSetDevice(device), "hipSetDevice");
-    if (!prog || prog->npx != npx || prog->device != device) {
-        if (firstSample != 0) throw std::invalid_argument(who + ": the tiles changed since the last call");
-        prog = std::make_shared<Progressive>();
-        prog->device = device;
-        prog->npx = npx;
-        hip_check(hipMalloc((void**)&prog->accum, std::max<size_t>(1, npx) * 6 * sizeof(float)), "hipMalloc");
-        hip_check(hipMalloc((void**)&prog->rgb, std::max<size_t>(1, npx) * 3 * sizeof(float)), "hipMalloc");
-        hip_check(hipMalloc((void**)&prog->rgba, std::max<size_t>(1, npx) * 4), "hipMalloc");
-    }
+    const size_t npx = q.npx;
+    PassBuffers::continue_at(prog, *this, scene, who, firstSample, samplesDone, npx, {6 * sizeof(float), 3 * sizeof(float), 4});
+    float *accum = (float*)prog->p[0], *dRgb = (float*)prog->p[1];
+    uint8_t* dRgba = (uint8_t*)prog->p[2];
     auto t0 = std::chrono::steady_clock::now();
-    float* rgbOut[1] = {prog->rgb};
-    uint8_t* rgbaOut[1] = {prog->rgba};
+    float* rgbOut[1] = {dRgb};
+    uint8_t* rgbaOut[1] = {dRgba};
     std::vector<int> counts;
     uint64_t samplesTaken = (uint64_t)npx * (uint64_t)nSamples;
     if (adaptive) {
         int32_t* dCounts = nullptr;
         hip_check(hipMalloc((void**)&dCounts, std::max<size_t>(1, npx) * sizeof(int32_t)), "hipMalloc");
         pbr_adaptive_result res;
-        const int rc = pbr_hip_render_adaptive(ctx, &rd, adaptive, prog->accum, dCounts, prog->rgb, prog->rgba, &res);
+        const int rc = pbr_hip_render_adaptive(ctx, &rd, adaptive, accum, dCounts, dRgb, dRgba, &res);
         counts.resize(npx);
         const hipError_t e = rc == PBR_OK ? hipMemcpy(counts.data(), dCounts, npx * sizeof(int32_t), hipMemcpyDeviceToHost) : hipSuccess;
         (void)hipFree(dCounts);
@@ -1735,26 +1683,15 @@ std::vector<int> SamplerIntegrator::RenderPass(const Scene& scene, const char* w
         samplesDone = 0;   // (the pixels' counts differ: no image a RenderSamples pass could continue)
         samplesTaken = (uint64_t)res.samples;
     } else {
-        check(ctx, pbr_hip_render_passes(ctx, &rd, firstSample, nSamples, 1, prog->accum, rgbOut, rgbaOut), "pbr_hip_render_passes");
+        check(ctx, pbr_hip_render_passes(ctx, &rd, firstSample, nSamples, 1, accum, rgbOut, rgbaOut), "pbr_hip_render_passes");
         check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
         samplesDone = firstSample + nSamples;
     }
     std::vector<float> rgb(npx * 3);
     std::vector<uint8_t> rgba(npx * 4);
-    hip_check(hipMemcpy(rgb.data(), prog->rgb, rgb.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
-    hip_check(hipMemcpy(rgba.data(), prog->rgba, rgba.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-    if (m_FrameBuffer) {
-        if (m_FrameBuffer->width != W || m_FrameBuffer->height != H || m_FrameBuffer->channals < 3)
-            throw std::invalid_argument(who + ": FrameBuffer not initialised to the pixel bounds");
-        size_t k = 0;
-        for (const pbr_tile& t : tl)
-            for (int y = t.y0; y < t.y1; ++y)
-                for (int x = t.x0; x < t.x1; ++x, ++k)
-                    for (int ch = 0; ch < m_FrameBuffer->channals; ++ch) {   // (flipped, as Render: Integrator.cpp:341-344)
-                        m_FrameBuffer->set_uc(x, H - y - 1, ch, rgba[4 * k + ch]);
-                        m_FrameBuffer->set_fc(x, H - y - 1, ch, ch < 3 ? rgb[3 * k + ch] : 1.f);
-                    }
-    }
+    hip_check(hipMemcpy(rgb.data(), dRgb, rgb.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(rgba.data(), dRgba, rgba.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+    write_framebuffer(m_FrameBuffer, who, q.tl, rgb.data(), rgba.data(), q.W, q.H);
     stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     stats.kernel_ms = 0;   // (passes are enqueued without event timing)
     stats.samples = samplesTaken;
@@ -1796,15 +1733,12 @@ struct SamplerIntegrator::MultiGPU {
 
 void SamplerIntegrator::RenderMulti(const Scene& scene, double& timeConsume) {
     auto t0 = std::chrono::steady_clock::now();
-    auto* cam = dynamic_cast<const PerspectiveCamera*>(camera.get());
-    if (!cam) throw std::invalid_argument("Render: only PerspectiveCamera is on the GPU path");
-    check_sampler(*sampler, *cam, "Render");
+    FrameRequest q(*this, scene, "Render");   // (the descriptor; each rank renders its own tiles)
+    const PerspectiveCamera* cam = q.cam;
     if (sampler->DeviceSampler() == PBR_SAMPLER_TABLE)
         throw std::invalid_argument("Render on several devices: custom GlobalSamplers render on one device");
     if (!tiles.empty()) throw std::invalid_argument("Render: SetTiles and SetDevices are exclusive");
-    const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;
-    if (W <= 0 || H <= 0 || W > cam->RasterWidth || H > cam->RasterHeight)
-        throw std::invalid_argument("Render: pixelBounds outside the camera raster");
+    const int W = q.W, H = q.H;
     if (!m_FrameBuffer || m_FrameBuffer->width != W || m_FrameBuffer->height != H || m_FrameBuffer->channals < 3)
         throw std::invalid_argument("Render: FrameBuffer not initialised to the pixel bounds");
     const int world = (int)devices.size();
@@ -1849,17 +1783,8 @@ void SamplerIntegrator::RenderMulti(const Scene& scene, double& timeConsume) {
         multi = m;
     }
     MultiGPU& m = *multi;
-    auto flat = FlattenScene(scene, cam->medium);
-    pbr_render_desc rd;
-    std::memset(&rd, 0, sizeof(rd));
-    rd.integrator = IntegratorType();
-    rd.max_depth = MaxDepth();
-    rd.rr_threshold = RRThreshold();
-    rd.light_strategy = LightStrategy();
-    rd.sampler = sampler->DeviceSampler();
-    rd.spp = (int)sampler->samplesPerPixel;
-    camera_desc(*cam, &rd.camera);
-    rd.camera.medium = MediumIndex(*flat, cam->medium);
+    const std::shared_ptr<FlatScene>& flat = q.flat;
+    pbr_render_desc& rd = q.rd;
     rd.outputs_on_device = 1;
     // every rank's frame is enqueued on its own stream (asynchronous: no stats, device outputs)
     std::vector<std::vector<pbr_tile>> tl(world);
@@ -1912,13 +1837,7 @@ void SamplerIntegrator::RenderMulti(const Scene& scene, double& timeConsume) {
         AssembleTiles(m.tiles[r], &u8[(size_t)r * m.maxPx * 4], 4, W, frameU8.data());
         AssembleTiles(m.tiles[r], &f32[(size_t)r * m.maxPx * 3], 3, W, frameF.data());
     }
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x)
-            for (int ch = 0; ch < m_FrameBuffer->channals; ++ch) {
-                const size_t k = (size_t)y * W + x;
-                m_FrameBuffer->set_uc(x, H - y - 1, ch, frameU8[4 * k + ch]);
-                m_FrameBuffer->set_fc(x, H - y - 1, ch, ch < 3 ? frameF[3 * k + ch] : 1.f);
-            }
+    write_framebuffer(m_FrameBuffer, "Render", {{0, 0, W, H}}, frameF.data(), frameU8.data(), W, H);   // (row-major: one tile)
     stats.samples = (uint64_t)W * H * (uint64_t)rd.spp;
     timeConsume = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     stats.seconds = timeConsume;
