@@ -745,6 +745,14 @@ struct FeatureBuffers {
     std::vector<float> depth;      // 1 per pixel: the mean distance of the samples that hit; 0 where none did
     std::vector<float> coverage;   // 1 per pixel: the fraction of the samples that hit
 };
+// SamplerIntegrator::Denoise's parameters (pbr_denoise of pbr_hip.h; the defaults are the suggested ones).
+struct DenoiseParams {
+    int iterations = 5;        // 1..8 wavelet levels; level i steps 2^i pixels
+    bool demodulate = true;    // filter colour / first-hit albedo and multiply back
+    float sigmaL = 4.f;        // edge stopping on luminance against the local variance, ...
+    float sigmaN = 0.4f;       // ... on the mean shading normal, ...
+    float sigmaZ = 1.f;        // ... on the distance against its screen-space slope; +inf switches a term off
+};
 class SamplerIntegrator : public Integrator {
   public:
     SamplerIntegrator(std::shared_ptr<const Camera> camera, std::shared_ptr<Sampler> sampler, const Bounds2i& pixelBounds,
@@ -781,6 +789,13 @@ class SamplerIntegrator : public Integrator {
     // (its count is independent of RenderSamples').  Honours SetTiles: pixels outside the tiles are left 0.
     // Synchronous, single device; a custom (table) sampler throws.
     void RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out);
+    // The edge-avoiding à-trous filter (no reference counterpart; pbr_hip_denoise) over what RenderSamples
+    // and RenderFeatures have accumulated on the device: the filtered image of the RenderSamples samples
+    // done so far goes to the FrameBuffer, flipped as Render writes it.  The sums are left as they are, so
+    // passes may continue.  Throws std::invalid_argument when RenderSamples has done fewer than 2 samples or
+    // RenderFeatures none (a RenderAdaptive image cannot be filtered: its counts are not kept), when
+    // SetTiles or SetDevices is in force, or for parameters out of range.  Synchronous.
+    void Denoise(const DenoiseParams& params = DenoiseParams());
     // Uploads the scene to the integrator's device (BVHAccel build, lights, media); Render and Li
     // do it on first use.  The reference's SamplerIntegrator::Preprocess is a no-op hook.
     virtual void Preprocess(const Scene& scene, Sampler& sampler);

@@ -23,6 +23,7 @@
  *                           pbr_hip_adaptive_select and pbr_hip_render_passes_list are its two steps)
  *   pbr_hip_render_aov    — (none): per-pixel albedo, coverage, normal and depth of the first surface the
  *                           same camera samples see, in the same resumable passes (feature buffers)
+ *   pbr_hip_denoise       — (none): an edge-avoiding à-trous filter over those sums and feature buffers
  *   pbr_hip_destroy      — scene/integrator destructors
  *   pbr_hip_last_error    — (none; the reference fails silently)
  *   pbr_hip_sync          — (none; the reference's Render returns when the frame is done): waits
@@ -451,6 +452,37 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int first_
  * (either may be NULL when max_launches == 0); *n_launches is their total number. */
 int pbr_hip_plan_aov(int64_t n_pixels, int samples, int max_launches, int64_t* first_pixel, int64_t* n_launch_pixels,
                      int* n_launches);
+
+/* ---- denoise (no reference counterpart) ----
+ * An edge-avoiding à-trous filter (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017)
+ * over what the passes leave on the device: the six sums per pixel of pbr_hip_render_passes (accum), the
+ * 8-float image pbr_hip_render_aov writes to aov_out (aov), and optionally the per-pixel sample counts
+ * of pbr_hip_render_adaptive (counts; NULL: every pixel took `samples`).  A 5x5 B3-spline wavelet,
+ * `iterations` levels, level i stepping 2^i pixels, with edge stopping on the luminance scaled by the
+ * locally blurred variance of the pixel mean, on the mean shading normal and on the distance scaled by its
+ * screen-space slope; the variance is carried from level to level.  With demodulate the colour is divided
+ * by the first-hit albedo (1 where the samples missed) before the filter and multiplied back after it.
+ * Every operation is float32 in the order DESIGN §4.5 states, nothing fused, no transcendental: the
+ * result is pinned bit for bit by a float32 restatement (tests/denoise_expected.py).
+ * Buffers are device pointers over a frame in raster order, row 0 first (what a descriptor with
+ * n_tiles == 0 renders).  Outputs, each may be NULL but not all three: rgb_out 3 floats per pixel;
+ * rgba_out the film transform of rgb_out (the 8-bit pixels of a render); var_out 1 float per pixel, the
+ * filtered variance in the filter's domain (after demodulation, summed over the channels).
+ * Asynchronous on `stream` (NULL: the context's) with the ordering of pbr_hip_render_aov: calls on one
+ * stream follow each other, a call on another stream drains the context first, and
+ * pbr_hip_wait_frame(ctx, stream, 0) orders another stream after the call.  The working planes (64 bytes
+ * per pixel) live in the context: allocated on first use, grown when the frame grows, freed by
+ * pbr_hip_destroy.  No scene is needed.
+ * PBR_E_INVALID: NULL ctx, p, accum or aov; all outputs NULL; width or height < 1; width * height >= 2^31;
+ * iterations outside 1..8; a sigma that is <= 0 or NaN; counts == NULL with samples < 2. */
+typedef struct pbr_denoise {
+    int width, height;     /* the frame: buffers are row-major, row 0 first */
+    int iterations;        /* 1..8 levels; level i steps 2^i pixels */
+    int demodulate;        /* 1: filter colour / albedo and multiply back */
+    float sigma_l, sigma_n, sigma_z;   /* > 0, +inf switches a term off; suggested defaults 4, 0.4, 1 */
+} pbr_denoise;
+int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const int32_t* counts, const float* accum,
+                    const float* aov, float* rgb_out, uint8_t* rgba_out, float* var_out, void* stream);
 
 /* ---- schedule (no reference counterpart) ----
  * How a frame is cut into launches on the device.  Every setting renders the same bits (the GPU

@@ -188,6 +188,43 @@ class HipRenderer:
                     "render_aov")
 
     @staticmethod
+    def _check_denoise(who, width, height, samples, have_counts, iterations, sigma_l, sigma_n, sigma_z):
+        """The frame and filter parameters of a denoise call, refused before any library call; returns
+        them as a capi.Denoise (demodulate left 0)."""
+        width, height, samples, iterations = int(width), int(height), int(samples), int(iterations)
+        if width < 1 or height < 1:
+            raise ValueError(f"{who}: width and height must be >= 1")
+        if width * height >= 1 << 31:
+            raise ValueError(f"{who}: width * height must be below 2^31")
+        if not 1 <= iterations <= 8:
+            raise ValueError(f"{who}: iterations must be 1..8")
+        for name, v in (("sigma_l", sigma_l), ("sigma_n", sigma_n), ("sigma_z", sigma_z)):
+            if not float(v) > 0.0:   # (a NaN fails the comparison)
+                raise ValueError(f"{who}: {name} must be > 0 (inf switches the term off)")
+        if not have_counts and samples < 2:
+            raise ValueError(f"{who}: samples must be >= 2 (a variance needs two), or give per-pixel counts")
+        return capi.Denoise(width, height, iterations, 0, float(sigma_l), float(sigma_n), float(sigma_z))
+
+    def denoise(self, width, height, samples, accum_ptr, aov_ptr, rgb_ptr=None, rgba_ptr=None, var_ptr=None, counts_ptr=None,
+                iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0, stream: int | None = None):
+        """The edge-avoiding à-trous filter (pbr_hip_denoise) over a width x height frame in raster order:
+        accum_ptr the 6 sums per pixel of render_passes, aov_ptr the 8-float image of render_aov, counts_ptr
+        (or None: every pixel took `samples`) the int32 per-pixel sample counts of render_adaptive.
+        `iterations` levels of a 5x5 B3-spline wavelet, level i stepping 2^i pixels, edge-stopped on
+        luminance against the local variance (sigma_l), the mean normal (sigma_n) and the distance against
+        its slope (sigma_z); demodulate filters colour / albedo.  Outputs (device pointers, at least one):
+        rgb_ptr 3 float32 per pixel, rgba_ptr its 8-bit film transform, var_ptr the filtered variance.
+        Asynchronous, ordered as render_aov; wait_frame(stream, 0) orders another stream after it."""
+        p = self._check_denoise("denoise", width, height, samples, bool(counts_ptr), iterations, sigma_l, sigma_n, sigma_z)
+        if not accum_ptr or not aov_ptr:
+            raise ValueError("denoise: accum (6 float32 per pixel) and aov (8 float32 per pixel) are required")
+        if not (rgb_ptr or rgba_ptr or var_ptr):
+            raise ValueError("denoise: no output buffer")
+        p.demodulate = 1 if demodulate else 0
+        self._check(self.lib.pbr_hip_denoise(self.ctx, C.byref(p), int(samples), counts_ptr or None, accum_ptr, aov_ptr,
+                                             rgb_ptr or None, rgba_ptr or None, var_ptr or None, stream), "denoise")
+
+    @staticmethod
     def _check_rule(who, tolerance, floor):
         tolerance, floor = float(tolerance), float(floor)
         if not tolerance >= 0.0:   # (a NaN fails the comparison)
@@ -440,6 +477,7 @@ class ProgressiveRender:
         self._device = device
         self._features = bool(features)
         self._accum = self._rgb = self._rgba = self._stream = self._aov = self._aov_img = None
+        self._dn_rgb = self._dn_rgba = None
 
     def _check_step(self, n_samples, passes):
         n_samples, passes = int(n_samples), int(passes)
@@ -496,6 +534,33 @@ class ProgressiveRender:
         self._buffers()
         f = self._aov_img
         return {"albedo": f[:, 0:3], "coverage": f[:, 3], "normal": f[:, 4:7], "depth": f[:, 7]}
+
+    def denoise(self, iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0):
+        """The image after the samples done so far, filtered (HipRenderer.denoise over the carried sums
+        and the feature image): (rgb [n, 3] float32, rgba [n, 4] uint8) device tensors of its own, reused
+        by the next call.  Needs features=True, at least 2 samples per pixel, and a descriptor without
+        tiles (the filter works on a whole frame in raster order).  Asynchronous as step()."""
+        if not self._features:
+            raise ValueError("ProgressiveRender.denoise: constructed with features=False")
+        if self.rdesc.n_tiles:
+            raise ValueError("ProgressiveRender.denoise: a tiled descriptor (the filter would stop at the tiles' borders)")
+        if self.samples_done < 2:
+            raise ValueError("ProgressiveRender.denoise needs at least 2 samples per pixel")
+        w, h = self.rdesc.camera.width, self.rdesc.camera.height
+        HipRenderer._check_denoise("ProgressiveRender.denoise", w, h, self.samples_done, False, iterations, sigma_l, sigma_n,
+                                   sigma_z)
+        torch = self._buffers()
+        if self._dn_rgb is None:
+            self._dn_rgb = torch.empty((self.n_pixels, 3), dtype=torch.float32, device=self._accum.device)
+            self._dn_rgba = torch.empty((self.n_pixels, 4), dtype=torch.uint8, device=self._accum.device)
+        current = torch.cuda.current_stream(self._accum.device)
+        self._stream.wait_stream(current)   # (readers of the last denoised image)
+        self.renderer.denoise(w, h, self.samples_done, self._accum.data_ptr(), self._aov_img.data_ptr(),
+                              rgb_ptr=self._dn_rgb.data_ptr(), rgba_ptr=self._dn_rgba.data_ptr(), iterations=iterations,
+                              demodulate=demodulate, sigma_l=sigma_l, sigma_n=sigma_n, sigma_z=sigma_z,
+                              stream=self._stream.cuda_stream)
+        current.wait_stream(self._stream)
+        return self._dn_rgb, self._dn_rgba
 
     def variance(self):
         """Per-pixel, per-channel sample variance [n_pixels, 3] (device tensor) from the two carried

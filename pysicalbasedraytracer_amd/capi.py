@@ -297,6 +297,12 @@ def plan_aov(n_pixels, samples, lib=None) -> list:
     return [(int(first[i]), int(count[i])) for i in range(n.value)]
 
 
+class Denoise(C.Structure):
+    """pbr_denoise: the frame and the filter's parameters (pbr_hip_denoise)."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("iterations", C.c_int), ("demodulate", C.c_int),
+                ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
+
+
 # Every symbol include/pbr_hip.h declares, with its ctypes signature.
 EXPORTS = {
     "pbr_hip_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -320,6 +326,8 @@ EXPORTS = {
     "pbr_hip_render_aov": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pbr_hip_plan_aov": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_int)]),
+    "pbr_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(Denoise), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbr_hip_get_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int)]),
     "pbr_hip_sampler_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -363,7 +371,7 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_set_schedule", "pbr_hip_sample_index", "pbr_hip_sample_dimensions",
                    "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk",
                    "pbr_hip_plan_chunks", "pbr_hip_last_chunks", "pbr_hip_adaptive_select", "pbr_hip_render_passes_list",
-                   "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov")
+                   "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov", "pbr_hip_denoise")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

@@ -572,25 +572,27 @@ __device__ __forceinline__ void pixel_xy(const KParams& P, long long q, int* x, 
 }
 
 // Output transform (Integrator.cpp:313-344): average, XYZ round trip, sRGB gamma, 8-bit.
+// film_rgba8: the transform's arithmetic on an averaged colour (shared with the denoiser's finish).
+__device__ __forceinline__ uint32_t film_rgba8(rgb col) {
+    float X = 0.412453f * col.r + 0.357580f * col.g + 0.180423f * col.b;
+    float Y = 0.212671f * col.r + 0.715160f * col.g + 0.072169f * col.b;
+    float Z = 0.019334f * col.r + 0.119193f * col.g + 0.950227f * col.b;
+    float o[3];
+    o[0] = 3.240479f * X - 1.537150f * Y - 0.498535f * Z;
+    o[1] = -0.969256f * X + 1.875991f * Y + 0.041556f * Z;
+    o[2] = 0.055648f * X - 0.204043f * Y + 1.057311f * Z;
+    uint32_t packed = 0xff000000u;
+    for (int k = 0; k < 3; ++k) {
+        float v = o[k];
+        float gc = (v <= 0.0031308f) ? 12.92f * v : 1.055f * t_pow(v, (1.f / 2.4f)) - 0.055f;
+        float b = clampf(255.f * gc + 0.5f, 0.f, 255.f);
+        packed |= ((uint32_t)(int)b & 0xffu) << (8 * k);
+    }
+    return packed;
+}
 __device__ __forceinline__ void film_write(const KParams& P, long long q, rgb col) {
     if (P.rgbOut) { P.rgbOut[3 * q] = col.r; P.rgbOut[3 * q + 1] = col.g; P.rgbOut[3 * q + 2] = col.b; }
-    if (P.rgbaOut) {
-        float X = 0.412453f * col.r + 0.357580f * col.g + 0.180423f * col.b;
-        float Y = 0.212671f * col.r + 0.715160f * col.g + 0.072169f * col.b;
-        float Z = 0.019334f * col.r + 0.119193f * col.g + 0.950227f * col.b;
-        float o[3];
-        o[0] = 3.240479f * X - 1.537150f * Y - 0.498535f * Z;
-        o[1] = -0.969256f * X + 1.875991f * Y + 0.041556f * Z;
-        o[2] = 0.055648f * X - 0.204043f * Y + 1.057311f * Z;
-        uint32_t packed = 0xff000000u;
-        for (int k = 0; k < 3; ++k) {
-            float v = o[k];
-            float gc = (v <= 0.0031308f) ? 12.92f * v : 1.055f * t_pow(v, (1.f / 2.4f)) - 0.055f;
-            float b = clampf(255.f * gc + 0.5f, 0.f, 255.f);
-            packed |= ((uint32_t)(int)b & 0xffu) << (8 * k);
-        }
-        reinterpret_cast<uint32_t*>(P.rgbaOut)[q] = packed;
-    }
+    if (P.rgbaOut) reinterpret_cast<uint32_t*>(P.rgbaOut)[q] = film_rgba8(col);
 }
 __device__ __forceinline__ void film_out(const KParams& P, long long q, rgb col) { film_write(P, q, col / (float)P.spp); }
 
@@ -677,6 +679,7 @@ __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
 #include "pbr_wavefront_volpath.h"
 #include "pbr_adaptive.h"
 #include "pbr_aov.h"
+#include "pbr_denoise.h"
 
 // ---------------------------------------------------------------- introspection kernels
 __global__ void k_sampler_values(DeviceSampler smp, HaltonParams hp, int n, const int32_t* q, float* out) {
@@ -970,6 +973,7 @@ struct pbr_hip_ctx {
     DevBuf dInfTex, dInfCF, dInfCC, dInfMF, dInfMC, dInfRec;
     DevBuf dTexels, dTextures, dTexMats;   // ImageTextures and the textured materials' parameters
     DevBuf dAlbedo;                        // per material: the feature buffers' albedo (pbr_aov.h)
+    DevBuf dDnXV[2], dDnNZ, dDnGB;         // the denoiser's working planes (pbr_denoise.h), 16 B per pixel each
     DevBuf dNodes, dWide, dQuad, dTri, dInfo, dUV, dSph, dMat, dLights, dEnv, dCdf, dFunc, dMedia;
     DevBuf dPrimes, dRecips, dPrimeSums, dPerms, dPrimIds;
     DevBuf dSobol, dSobolHi, dSobolPix;  // active Sobol nibble tables (index bits 0-31, 32-51), pixel tables
@@ -2828,6 +2832,82 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
     return hand_off_guard(ctx, s, true);
 }
 
+// ---- denoise (pbr_denoise.h)
+int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const int32_t* counts, const float* accum,
+                    const float* aov, float* rgb_out, uint8_t* rgba_out, float* var_out, void* stream) {
+    if (!ctx) return PBR_E_INVALID;
+    if (!p) return set_err(ctx, PBR_E_INVALID, "denoise: null parameters");
+    if (!accum || !aov) return set_err(ctx, PBR_E_INVALID, "denoise: accum (6 floats per pixel) and aov (8 floats per pixel) are required");
+    if (!rgb_out && !rgba_out && !var_out) return set_err(ctx, PBR_E_INVALID, "denoise: no output");
+    if (p->width < 1 || p->height < 1) return set_err(ctx, PBR_E_INVALID, "denoise: width and height must be >= 1");
+    if ((long long)p->width * p->height >= (1ll << 31)) return set_err(ctx, PBR_E_INVALID, "denoise: width * height must be below 2^31");
+    if (p->iterations < 1 || p->iterations > 8) return set_err(ctx, PBR_E_INVALID, "denoise: iterations must be 1..8");
+    if (!(p->sigma_l > 0.f) || !(p->sigma_n > 0.f) || !(p->sigma_z > 0.f))
+        return set_err(ctx, PBR_E_INVALID, "denoise: sigma_l, sigma_n and sigma_z must be > 0");
+    if (!counts && samples < 2) return set_err(ctx, PBR_E_INVALID, "denoise: samples must be >= 2 (or give per-pixel counts)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    // the working planes are the context's: as a pass, a call on another stream drains the context first
+    if (ctx->lastStream != s) {
+        if (int rc = drain(ctx)) return rc;
+    }
+    const int W = p->width, H = p->height;
+    const long long npx = (long long)W * H;
+    const size_t plane = (size_t)npx * sizeof(float4);
+    if (ctx->dDnXV[0].bytes < plane) {   // (growing frees planes an earlier call on this stream may still use)
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(ctx->dDnXV[0].ensure(plane));
+        HIP_TRY(ctx->dDnXV[1].ensure(plane));
+        HIP_TRY(ctx->dDnNZ.ensure(plane));
+        HIP_TRY(ctx->dDnGB.ensure(plane));
+    }
+    float4* xv[2] = {(float4*)ctx->dDnXV[0].p, (float4*)ctx->dDnXV[1].p};
+    float4* nz = (float4*)ctx->dDnNZ.p;
+    float4* gb = (float4*)ctx->dDnGB.p;
+    const int nbx = (W + kDnTW - 1) / kDnTW, nby = (H + kDnTH - 1) / kDnTH;
+    const dim3 grid((unsigned)((long long)nbx * nby)), blk(kDnBlock);   // (below 2^31 tiles: npx is)
+    ctx->batchFrames = 0;   // (set when the call is queued)
+    begin_lanes(ctx, s);
+    PROF_LAUNCH(KP_DN_PREPARE, s,
+        hipLaunchKernelGGL(k_dn_prepare, grid, blk, 0, s, W, H, nbx, samples, p->demodulate ? 1 : 0, counts, accum, aov, xv[0], nz, gb));
+    prof_host(ctx, KP_DN_PREPARE, 0, (unsigned long long)npx);
+    if (counts) prof_host(ctx, KP_DN_PREPARE, 1, (unsigned long long)npx);
+    DnParams D;
+    std::memset(&D, 0, sizeof(D));
+    D.W = W;
+    D.H = H;
+    D.nbx = nbx;
+    D.il = 1.f / (p->sigma_l * p->sigma_l);
+    D.in = 1.f / (p->sigma_n * p->sigma_n);
+    D.iz = 1.f / (p->sigma_z * p->sigma_z);
+    D.nz = nz;
+    D.gb = gb;
+    for (int i = 0; i < p->iterations; ++i) {
+        D.step = 1 << i;
+        D.xvIn = xv[i & 1];
+        D.xvOut = xv[(i & 1) ^ 1];
+        const int lds = i < kDnLdsLevels ? D.step : 0;
+        PROF_LAUNCH(KP_DN_LEVEL0 + i, s,
+            if (lds == 1) hipLaunchKernelGGL(k_dn_atrous_lds<1>, grid, blk, 0, s, D);
+            else if (lds == 2) hipLaunchKernelGGL(k_dn_atrous_lds<2>, grid, blk, 0, s, D);
+            else if (lds == 4) hipLaunchKernelGGL(k_dn_atrous_lds<4>, grid, blk, 0, s, D);
+            else hipLaunchKernelGGL(k_dn_atrous, grid, blk, 0, s, D));
+        prof_host(ctx, KP_DN_LEVEL0 + i, 0, (unsigned long long)npx);
+    }
+    PROF_LAUNCH(KP_DN_FINISH, s,
+        hipLaunchKernelGGL(k_dn_finish, dim3((unsigned)((npx + kDnBlock - 1) / kDnBlock)), blk, 0, s, npx,
+                           (const float4*)xv[p->iterations & 1], (const float4*)gb, rgb_out, (uint32_t*)rgba_out, var_out));
+    HIP_TRY(hipGetLastError());
+    prof_host(ctx, KP_DN_FINISH, 0, (unsigned long long)npx);
+    if (rgb_out) prof_host(ctx, KP_DN_FINISH, 1, (unsigned long long)npx);
+    if (rgba_out) prof_host(ctx, KP_DN_FINISH, 2, (unsigned long long)npx);
+    if (var_out) prof_host(ctx, KP_DN_FINISH, 3, (unsigned long long)npx);
+    if (int rc = one_pass_done(ctx, s)) return rc;
+    ctx->inFlight = true;
+    ctx->lastStream = s;
+    return PBR_OK;
+}
+
 int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f) {
     if (!ctx) return PBR_E_INVALID;
     if (f < 0 || f >= ctx->batchFrames) return set_err(ctx, PBR_E_INVALID, "wait_frame: no such frame in the last batch");
@@ -2929,7 +3009,9 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
     static const char* kNames[KP_COUNT] = {
         "k_wf_camera_extend", "k_wf_shade", "k_wf_shadow", "k_wf_extend", "k_wf_finish",
         "k_wfp_camera_extend", "k_wfp_shade", "k_wfp_shadow", "k_wfp_probe", "k_wfp_resolve", "k_wfp_finish",
-        "k_wfv_shade", "k_wfv_tr", "k_wfv_resolve", "k_render", "k_wf_shade_l0", "k_aov", "k_aov_tex"};
+        "k_wfv_shade", "k_wfv_tr", "k_wfv_resolve", "k_render", "k_wf_shade_l0", "k_aov", "k_aov_tex",
+        "k_dn_prepare", "k_dn_atrous_l0", "k_dn_atrous_l1", "k_dn_atrous_l2", "k_dn_atrous_l3", "k_dn_atrous_l4",
+        "k_dn_atrous_l5", "k_dn_atrous_l6", "k_dn_atrous_l7", "k_dn_finish"};
     unsigned long long c[KP_COUNT][kProfFields];
     std::memset(c, 0, sizeof(c));
     if (ctx->profOn) HIP_TRY(hipMemcpy(c, ctx->dProf.p, sizeof(c), hipMemcpyDeviceToHost));
@@ -2973,7 +3055,14 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         case KP_WFV_RESOLVE: return 140 * f[0];
         // f[1] pixels: the sums written; f[2] of them continue (the sums read); f[3] write the image
         case KP_AOV: case KP_AOV_TEX: return 32 * (f[1] + f[2] + f[3]);
-        default: return 16 * f[1];                                             // megakernel: the film output
+        // the denoiser, f[0] pixels.  prepare: sums 24 + features 32 (+ 4 per count, f[1]) read, three
+        // planes written; a level: colour and guides read, colour written; finish: colour and divisor
+        // read, f[1] rgb, f[2] rgba and f[3] variance pixels written
+        case KP_DN_PREPARE: return 104 * f[0] + 4 * f[1];
+        case KP_DN_FINISH: return 32 * f[0] + 12 * f[1] + 4 * f[2] + 4 * f[3];
+        default:
+            if (k >= KP_DN_LEVEL0 && k < KP_DN_LEVEL0 + 8) return 48 * f[0];
+            return 16 * f[1];                                                  // megakernel: the film output
         }
     };
     int m = 0;

@@ -39,6 +39,8 @@ enum ProfKind {
     KP_WFV_SHADE, KP_WFV_TR, KP_WFV_RESOLVE, KP_MEGA,
     KP_WF_SHADE0,   // k_wf_shade's fused level-0 launches (camera rays traced in the shade): own family
     KP_AOV, KP_AOV_TEX,   // feature passes (pbr_aov.h): the untextured and the textured instantiations
+    // the denoiser (pbr_denoise.h): prepare, one family per wavelet level (8 of them), finish
+    KP_DN_PREPARE, KP_DN_LEVEL0, KP_DN_FINISH = KP_DN_LEVEL0 + 8,
     KP_COUNT
 };
 constexpr int kProfFields = 8;

@@ -1652,6 +1652,36 @@ void SamplerIntegrator::RenderFeatures(const Scene& scene, int firstSample, int 
             }
 }
 
+void SamplerIntegrator::Denoise(const DenoiseParams& params) {
+    const std::string who("Denoise");
+    if (params.iterations < 1 || params.iterations > 8) throw std::invalid_argument(who + ": iterations must be 1..8");
+    if (!(params.sigmaL > 0.f) || !(params.sigmaN > 0.f) || !(params.sigmaZ > 0.f))
+        throw std::invalid_argument(who + ": sigmaL, sigmaN and sigmaZ must be > 0");
+    if (!tiles.empty())
+        throw std::invalid_argument(who + ": SetTiles is in force (the filter works on a whole frame, not across tile borders)");
+    if (!devices.empty()) throw std::invalid_argument(who + ": one device (SetDevice), not SetDevices");
+    if (!prog || samplesDone < 2)
+        throw std::invalid_argument(who + ": RenderSamples has accumulated " + std::to_string(prog ? samplesDone : 0) +
+                                    " samples; a variance needs 2");
+    if (!feat || featuresDone < 1) throw std::invalid_argument(who + ": RenderFeatures has accumulated no samples");
+    const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;
+    const size_t npx = (size_t)W * H;
+    if (prog->npx != npx || feat->npx != npx || prog->device != device || feat->device != device)
+        throw std::invalid_argument(who + ": the accumulated passes are not whole frames of the pixel bounds on this device");
+    hip_check(hipSetDevice(device), "hipSetDevice");
+    const pbr_denoise p = {W, H, params.iterations, params.demodulate ? 1 : 0, params.sigmaL, params.sigmaN, params.sigmaZ};
+    float* dRgb = (float*)prog->p[1];
+    uint8_t* dRgba = (uint8_t*)prog->p[2];
+    check(ctx, pbr_hip_denoise(ctx, &p, samplesDone, nullptr, (const float*)prog->p[0], (const float*)feat->p[1], dRgb, dRgba,
+                               nullptr, nullptr), "pbr_hip_denoise");
+    check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
+    std::vector<float> rgb(npx * 3);
+    std::vector<uint8_t> rgba(npx * 4);
+    hip_check(hipMemcpy(rgb.data(), dRgb, rgb.size() * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(rgba.data(), dRgba, rgba.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+    write_framebuffer(m_FrameBuffer, who, {pbr_tile{0, 0, W, H}}, rgb.data(), rgba.data(), W, H);
+}
+
 // One pass of RenderSamples, or (adaptive != nullptr) a whole adaptive render from sample 0; returns
 // the adaptive render's per-pixel sample counts in packed tile order.
 std::vector<int> SamplerIntegrator::RenderPass(const Scene& scene, const char* whoName, int firstSample, int nSamples,
