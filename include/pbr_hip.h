@@ -658,6 +658,73 @@ int pbr_hip_bounds(pbr_hip_ctx* ctx, int prim, float* out6);
 int pbr_hip_li(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int n, const float* rays,
                const int32_t* px_py_sample_dim, int depth, float* rgb_out);
 
+/* ---- the scattering layer on caller-given directions ----
+ * BSDF::f, Pdf and Sample_f (Material/Reflection.cpp:56-164) of the uploaded scene's materials, one
+ * query per lane, through the functions the shading kernels call (pbr_device.h bsdf_f, bsdf_pdf,
+ * bsdf_f_pdf, bsdf_sample, bsdf_sample_dir + bsdf_sample_sum).  The BSDF is built as
+ * ComputeScatteringFunctions builds it at a hit: lobe template 2 * material + multi_lobe, frame
+ * ss = normalize(dpdu), ts = cross(ns, ss).  All directions are world directions. */
+typedef struct pbr_bsdf_query {
+    int material;               /* index into the scene's materials; outside it, or PBR_MAT_NONE: no BSDF */
+    int multi_lobe;             /* allowMultipleLobes (Whitted 0, Path / VolPath 1) */
+    int type;                   /* BxDFType mask (BSDF_REFLECTION 1, TRANSMISSION 2, DIFFUSE 4, GLOSSY 8, SPECULAR 16) */
+    int pad0;
+    float n[3], ns[3], dpdu[3]; /* geometric normal, shading normal, shading dpdu */
+    float uv[2];                /* surface (u, v): read by image-textured materials only */
+    float wo[3], wi[3];
+    float u0, u1;               /* the sample of Sample_f */
+    float pad1;
+} pbr_bsdf_query;
+/* pdf and sampled type are set to -1 before each sample call, wi to 0: BSDF::Sample_f leaves *pdf
+ * (and the type) untouched when wo lies in the shading tangent plane (Reflection.cpp:121), and so
+ * does the record.  wi is meaningful only where the sample's pdf is not 0. */
+typedef struct pbr_bsdf_record {
+    int no_bsdf;                /* 1: material == nullptr or out of range; every other field is 0 */
+    float f[3];                 /* bsdf_f */
+    float pdf;                  /* bsdf_pdf */
+    float f_lam[3], pdf_lam;    /* bsdf_f_pdf given Lambda(wo) (mf_lambda), as Path and VolPath call it */
+    float f_nolam[3], pdf_nolam;/* bsdf_f_pdf without it */
+    float s_wi[3], s_f[3], s_pdf;   /* bsdf_sample */
+    int s_type;
+    float d_wi[3], d_f[3], d_pdf;   /* bsdf_sample_dir given Lambda(wo), then bsdf_sample_sum */
+    int d_type;
+    int d_ok;                   /* what bsdf_sample_dir returned; 0: the sum was not formed (d_f = 0) */
+    int pad[2];
+} pbr_bsdf_record;
+/* The instantiation evaluated: the lobe mask a production shading kernel is compiled under (kinds
+ * outside it compile out) and where it reads the lobe templates.  A mask that does not cover the
+ * scene's lobe kinds is refused (PBR_E_INVALID): no render launches that, and its result is
+ * meaningless.  The probe kernel is compiled apart from the shading kernels; the library is built
+ * without contraction or fast-math and with correctly rounded division and square root, so the
+ * source and the mask fix every bit, and the probe's bits are the shading kernels'. */
+enum pbr_bsdf_variant {
+    PBR_BSDF_ALL = 0,           /* every lobe kind; templates from LDS when they fit (32), else global memory */
+    PBR_BSDF_SIMPLE = 1,        /* Lambert, Oren-Nayar, specular (Whitted / Path without microfacets) */
+    PBR_BSDF_MATTE_MIRROR = 2,  /* Lambert + mirror (C2, C3) */
+    PBR_BSDF_MICRO = 3,         /* Lambert + microfacet reflection / transmission (C4, C5) */
+    PBR_BSDF_PASS_L = 4,        /* the classed shade's passes: Lambert */
+    PBR_BSDF_PASS_R = 5,        /* microfacet reflection */
+    PBR_BSDF_PASS_LR = 6,       /* Lambert + microfacet reflection */
+    PBR_BSDF_PASS_RT = 7,       /* microfacet reflection + transmission */
+    PBR_BSDF_PASS_LRT = 8,      /* = PBR_BSDF_MICRO's mask, as the last pass instantiates it */
+    PBR_BSDF_MIRROR = 9,        /* specular reflection alone (Whitted's mirror bounce) */
+    PBR_BSDF_TEXTURED = 10,     /* every kind, image-textured materials' lobes built per hit; global memory */
+    PBR_BSDF_ALL_LDS = 11,      /* every kind, templates from the LDS copy (PBR_E_INVALID above 32 templates) */
+    PBR_BSDF_ALL_GLOBAL = 12    /* every kind, templates from global memory */
+};
+int pbr_hip_bsdf(pbr_hip_ctx* ctx, int variant, int n, const pbr_bsdf_query* queries, pbr_bsdf_record* out);
+/* The same functions compiled for the host, for one material with constant textures (query material
+ * 0; any other index: no BSDF), through the conversion pbr_hip_upload_scene applies to it.  No
+ * context, no GPU.  PBR_E_INVALID: an image-textured or unknown material, an unknown variant, a
+ * mask that does not cover the material's lobes. */
+int pbr_hip_bsdf_host(const pbr_material_desc* material, int variant, int n, const pbr_bsdf_query* queries,
+                      pbr_bsdf_record* out);
+/* HenyeyGreenstein::p and Sample_p (Media/Medium.h:24-27, Medium.cpp:9-26) as VolPath's shade calls
+ * them: queries = g, wo.xyz, wi.xyz, u0, u1 (9 floats); out = p(wo, wi), the sampled wi.xyz and its
+ * value (5 floats).  The _host form runs the same source on the CPU. */
+int pbr_hip_phase_hg(pbr_hip_ctx* ctx, int n, const float* queries, float* out);
+int pbr_hip_phase_hg_host(int n, const float* queries, float* out);
+
 /* ---- BVH construction (BVHAccel::BVHAccel, Accelerator/BVHAccel.cpp:57-87; SAH recursiveBuild
  * :97-260; flattenBVHTree :262-283) ----
  * Both builders produce the reference's node array and orderedPrims exactly (the host one is the

@@ -1998,6 +1998,69 @@ int oracle_intersect(const pbr_scene_desc* sd, int n, const float* rays, float* 
     }
 }
 
+// BSDF::f, Pdf and Sample_f of the scene's materials on caller-given directions, in the records of
+// pbr_hip_bsdf.  The restatement has one f, one Pdf and one Sample_f: the fused (f_lam, f_nolam) and
+// split (d_*) fields repeat them, which is what the device's forms claim to equal; d_ok is -1 (the
+// reference has no such return).  Each material is reached through a primitive added for it, so
+// ComputeBSDF runs as at a hit.
+int oracle_bsdf(const pbr_scene_desc* sd, int n, const pbr_bsdf_query* queries, pbr_bsdf_record* out) {
+    try {
+        std::unique_ptr<Scene> s = BuildScene(sd);
+        const int base = (int)s->prims.size();
+        for (int m = 0; m <= sd->n_materials; ++m) {
+            Prim pr = Prim();
+            pr.shape = -1; pr.tri = -1; pr.areaLight = -1; pr.medIn = -1; pr.medOut = -1;
+            pr.material = m < sd->n_materials ? mat_index(sd, m) : -1;
+            s->prims.push_back(pr);
+        }
+        for (int i = 0; i < n; ++i) {
+            const pbr_bsdf_query& q = queries[i];
+            pbr_bsdf_record& r = out[i];
+            std::memset(&r, 0, sizeof(r));
+            SurfaceInteraction si;
+            si.prim = base + ((q.material >= 0 && q.material < sd->n_materials) ? q.material : sd->n_materials);
+            si.n = V3(q.n[0], q.n[1], q.n[2]);
+            si.sn = V3(q.ns[0], q.ns[1], q.ns[2]);
+            si.dpdu = V3(q.dpdu[0], q.dpdu[1], q.dpdu[2]);
+            si.uv = P2(q.uv[0], q.uv[1]);
+            BSDF b;
+            ComputeBSDF(*s, si, q.multi_lobe != 0, &b);
+            if (!b.valid) { r.no_bsdf = 1; continue; }
+            const V3 wo(q.wo[0], q.wo[1], q.wo[2]), wi(q.wi[0], q.wi[1], q.wi[2]);
+            const Spec f = b.f(wo, wi, q.type);
+            const float pdf = b.Pdf(wo, wi, q.type);
+            for (int c = 0; c < 3; ++c) r.f[c] = r.f_lam[c] = r.f_nolam[c] = f[c];
+            r.pdf = r.pdf_lam = r.pdf_nolam = pdf;
+            V3 swi(0, 0, 0);
+            float spdf = -1.f;
+            int st = -1;
+            const Spec sf = b.Sample_f(wo, &swi, P2(q.u0, q.u1), &spdf, q.type, &st);
+            r.s_wi[0] = r.d_wi[0] = swi.x; r.s_wi[1] = r.d_wi[1] = swi.y; r.s_wi[2] = r.d_wi[2] = swi.z;
+            for (int c = 0; c < 3; ++c) r.s_f[c] = r.d_f[c] = sf[c];
+            r.s_pdf = r.d_pdf = spdf;
+            r.s_type = r.d_type = st;
+            r.d_ok = -1;
+        }
+        return 0;
+    } catch (const std::exception&) {
+        return PBR_E_INVALID;
+    }
+}
+
+// HenyeyGreenstein::p and Sample_p in the records of pbr_hip_phase_hg
+int oracle_phase_hg(int n, const float* queries, float* out) {
+    for (int i = 0; i < n; ++i) {
+        const float* q = queries + (size_t)9 * i;
+        float* o = out + (size_t)5 * i;
+        const V3 wo(q[1], q[2], q[3]), wi(q[4], q[5], q[6]);
+        o[0] = PhaseHG(Dot(wo, wi), q[0]);   // Medium.cpp:5-7
+        V3 swi(0, 0, 0);
+        o[4] = HGSample(q[0], wo, &swi, P2(q[7], q[8]));
+        o[1] = swi.x; o[2] = swi.y; o[3] = swi.z;
+    }
+    return 0;
+}
+
 int oracle_triangle_test(const float* tri, const float* r, float* out) {
     Ray ray(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), r[6]);
     float t = 0, b0 = 0, b1 = 0, b2 = 0;

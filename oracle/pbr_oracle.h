@@ -57,6 +57,11 @@ int oracle_li_pixel(const pbr_scene_desc* scene, const pbr_render_desc* desc, in
 /* Watertight triangle test on explicit data: tri = 9 floats, ray = 7 floats,
  * out = {hit, t, b0, b1, b2}. */
 int oracle_triangle_test(const float* tri, const float* ray, float* out);
+/* BSDF::f, Pdf and Sample_f of the scene's materials for the queries of pbr_hip_bsdf, in its records
+ * (the fused and split fields repeat f / Pdf / Sample_f; d_ok = -1). */
+int oracle_bsdf(const pbr_scene_desc* scene, int n, const pbr_bsdf_query* queries, pbr_bsdf_record* out);
+/* HenyeyGreenstein::p and Sample_p for the queries of pbr_hip_phase_hg, in its records. */
+int oracle_phase_hg(int n, const float* queries, float* out);
 int oracle_sizeof_linear_bvh_node(void);
 
 #ifdef __cplusplus

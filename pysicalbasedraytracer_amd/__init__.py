@@ -453,6 +453,23 @@ class HipRenderer:
                     "intersect_walk")
         return out
 
+    def bsdf(self, queries, variant=capi.BSDF_VARIANT_ALL):
+        """BSDF::f, Pdf and Sample_f of the uploaded scene's materials on caller-given directions,
+        under the lobe mask and template source of one production shading kernel
+        (capi.BSDF_VARIANT_*): capi.bsdf_query_dtype records in, capi.bsdf_record_dtype records out."""
+        q = np.ascontiguousarray(queries, dtype=capi.bsdf_query_dtype()).reshape(-1)
+        out = np.zeros(q.shape[0], dtype=capi.bsdf_record_dtype())
+        self._check(self.lib.pbr_hip_bsdf(self.ctx, int(variant), q.shape[0], q.ctypes.data, out.ctypes.data), "bsdf")
+        return out
+
+    def phase_hg(self, queries):
+        """HenyeyGreenstein::p and Sample_p on the device: [n, 9] (g, wo, wi, u0, u1) → [n, 5]
+        (p(wo, wi), the sampled wi, its value)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 9)
+        out = np.zeros((q.shape[0], 5), dtype=np.float32)
+        self._check(self.lib.pbr_hip_phase_hg(self.ctx, q.shape[0], capi.fptr(q), capi.fptr(out)), "phase_hg")
+        return out
+
 
 class ProgressiveRender:
     """A render that proceeds in sample passes and can stop, show, checkpoint and resume.

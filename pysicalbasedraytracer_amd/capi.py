@@ -303,8 +303,60 @@ class Denoise(C.Structure):
                 ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
 
 
+# enum pbr_bsdf_variant (pbr_hip_bsdf): the lobe mask and template source of a production shading kernel
+(BSDF_VARIANT_ALL, BSDF_VARIANT_SIMPLE, BSDF_VARIANT_MATTE_MIRROR, BSDF_VARIANT_MICRO, BSDF_VARIANT_PASS_L,
+ BSDF_VARIANT_PASS_R, BSDF_VARIANT_PASS_LR, BSDF_VARIANT_PASS_RT, BSDF_VARIANT_PASS_LRT, BSDF_VARIANT_MIRROR,
+ BSDF_VARIANT_TEXTURED, BSDF_VARIANT_ALL_LDS, BSDF_VARIANT_ALL_GLOBAL) = range(13)
+# BxDFType (Reflection.h:47-55)
+BSDF_REFLECTION, BSDF_TRANSMISSION, BSDF_DIFFUSE, BSDF_GLOSSY, BSDF_SPECULAR, BSDF_ALL = 1, 2, 4, 8, 16, 31
+
+
+def bsdf_query_dtype():
+    """pbr_bsdf_query as a numpy record type (96 bytes)."""
+    import numpy as np
+    return np.dtype([("material", "i4"), ("multi_lobe", "i4"), ("type", "i4"), ("pad0", "i4"), ("n", "f4", 3), ("ns", "f4", 3),
+                     ("dpdu", "f4", 3), ("uv", "f4", 2), ("wo", "f4", 3), ("wi", "f4", 3), ("u0", "f4"), ("u1", "f4"),
+                     ("pad1", "f4")])
+
+
+def bsdf_record_dtype():
+    """pbr_bsdf_record as a numpy record type (128 bytes)."""
+    import numpy as np
+    return np.dtype([("no_bsdf", "i4"), ("f", "f4", 3), ("pdf", "f4"), ("f_lam", "f4", 3), ("pdf_lam", "f4"),
+                     ("f_nolam", "f4", 3), ("pdf_nolam", "f4"), ("s_wi", "f4", 3), ("s_f", "f4", 3), ("s_pdf", "f4"),
+                     ("s_type", "i4"), ("d_wi", "f4", 3), ("d_f", "f4", 3), ("d_pdf", "f4"), ("d_type", "i4"), ("d_ok", "i4"),
+                     ("pad", "i4", 2)])
+
+
+def bsdf_host(material: "MaterialDesc", variant, queries, lib=None):
+    """pbr_hip_bsdf_host: the device's BSDF functions compiled for the CPU, on one constant material
+    (query material 0).  queries: bsdf_query_dtype records; returns bsdf_record_dtype records.
+    Raises ValueError where the library refuses (variant, mask, textured material)."""
+    import numpy as np
+    q = np.ascontiguousarray(queries, dtype=bsdf_query_dtype()).reshape(-1)
+    out = np.zeros(q.shape[0], dtype=bsdf_record_dtype())
+    rc = (lib or load_library()).pbr_hip_bsdf_host(C.byref(material), int(variant), q.shape[0], q.ctypes.data, out.ctypes.data)
+    if rc != PBR_OK:
+        raise ValueError(f"bsdf_host: refused ({rc})")
+    return out
+
+
+def phase_hg_host(queries, lib=None):
+    """pbr_hip_phase_hg_host: [n, 9] (g, wo, wi, u0, u1) → [n, 5] (p, sampled wi, its value)."""
+    import numpy as np
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 9)
+    out = np.zeros((q.shape[0], 5), dtype=np.float32)
+    if (lib or load_library()).pbr_hip_phase_hg_host(q.shape[0], fptr(q), fptr(out)) != PBR_OK:
+        raise ValueError("phase_hg_host: refused")
+    return out
+
+
 # Every symbol include/pbr_hip.h declares, with its ctypes signature.
 EXPORTS = {
+    "pbr_hip_bsdf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pbr_hip_bsdf_host": (C.c_int, [C.POINTER(MaterialDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pbr_hip_phase_hg": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pbr_hip_phase_hg_host": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "pbr_hip_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "pbr_hip_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "pbr_hip_render": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p, C.c_void_p,
@@ -371,7 +423,8 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_set_schedule", "pbr_hip_sample_index", "pbr_hip_sample_dimensions",
                    "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk",
                    "pbr_hip_plan_chunks", "pbr_hip_last_chunks", "pbr_hip_adaptive_select", "pbr_hip_render_passes_list",
-                   "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov", "pbr_hip_denoise")
+                   "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov", "pbr_hip_denoise", "pbr_hip_bsdf",
+                   "pbr_hip_bsdf_host", "pbr_hip_phase_hg", "pbr_hip_phase_hg_host")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

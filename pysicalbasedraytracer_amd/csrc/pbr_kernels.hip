@@ -25,6 +25,7 @@
 #include "pbr_scene.h"
 #include "pbr_chunk_plan.h"
 #include "pbr_aov_plan.h"
+#include "pbr_probe_glue.h"
 
 using namespace pbr;
 
@@ -1666,9 +1667,8 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
     // lobe sets (C4's glass, metal, plastic and matte), one launch per lobe set shades that set's hits
     // with a kernel compiled for it.  A material goes to the first of these sets that holds its lobes;
     // misses and material-less hits to pass 0.  VolPath: pass 0 is the medium pass (no lobes: the
-    // rays inside a medium, misses, material-less hits) and every lobe set present has a pass.
-    static constexpr int kPassLobes[] = {1 << L_LAMBERT, 1 << L_MF_R, (1 << L_LAMBERT) | (1 << L_MF_R),
-                                         (1 << L_MF_R) | (1 << L_MF_T), kMicroLobes};
+    // rays inside a medium, misses, material-less hits) and every lobe set present has a pass
+    // (kPassLobes, pbr_lobe_masks.h).
     constexpr int kMediumPassKind = 5;                          // VolPath's pass 0 (k_wfv_shade<0, …>)
     std::vector<int> passKind;                                   // pass → kPassLobes index
     std::vector<int32_t> matPass(ctx->host.materials.size() / 2, 0);
@@ -2028,6 +2028,28 @@ int make_params(pbr_hip_ctx* ctx, const pbr_render_desc* d, KParams* out) {
 }
 
 }  // namespace
+
+// ---- pbr_probe_glue.h: what a probe compiled in another translation unit needs of a context
+int pbr::probe_fail(pbr_hip_ctx* ctx, int code, const char* msg) { return set_err(ctx, code, msg); }
+int pbr::probe_scene_info(pbr_hip_ctx* ctx, int* lobeKinds, int* nTemplates) {
+    if (!ctx->haveScene) return set_err(ctx, PBR_E_NOSCENE, "no scene uploaded");
+    *lobeKinds = scene_lobe_kinds(ctx->host);
+    *nTemplates = (int)ctx->host.materials.size();
+    return PBR_OK;
+}
+int pbr::probe_round_trip(pbr_hip_ctx* ctx, int n, const void* in, size_t inBytes, void* out, size_t outBytes,
+                          const ProbeLaunch& launch) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = drain(ctx)) return rc;
+    if (n == 0) return PBR_OK;
+    return scratch_round_trip(ctx, n, in, inBytes, nullptr, 0, out, outBytes, [&](const char* dIn, const char*, void* dOut) {
+        DeviceScene S;
+        std::memset(&S, 0, sizeof(S));
+        if (ctx->haveScene) S = device_scene(ctx);
+        launch(S, ctx->stream, dIn, dOut);
+        return PBR_OK;
+    });
+}
 
 extern "C" {
 

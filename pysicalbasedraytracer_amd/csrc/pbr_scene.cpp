@@ -364,6 +364,8 @@ void distribution1d(const std::vector<float>& f, std::vector<float>* cdf, float*
 
 }  // namespace
 
+MatTemplate constant_material_template(const pbr_material_desc& m, bool multi) { return material_template(m, multi); }
+
 // InitInterior (BVHAccel.cpp:33-38) overwrites an interior node's box with Union(c0->bounds,
 // c1->bounds).  The builders reduce the range before partitioning it, which gives the same values;
 // only the sign of a zero can differ (Union keeps its first operand on ties, -0 == +0), so the

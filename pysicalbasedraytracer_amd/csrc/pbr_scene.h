@@ -89,6 +89,10 @@ void build_image_texture(const pbr_texture_desc& td, TexDev* out, std::vector<fl
 // Throws std::invalid_argument on a malformed descriptor.  `bvh` replaces the host SAH build.
 void build_host_scene(const pbr_scene_desc* desc, HostScene* out, const BvhBuildFn* bvh = nullptr);
 
+// A material's lobe template with its constant textures folded, as build_host_scene stores it
+// (allowMultipleLobes = multi).  Throws std::invalid_argument on an unknown material type.
+MatTemplate constant_material_template(const pbr_material_desc& m, bool multi);
+
 // Light sampling distribution (Distribution1D over lights): uniform or power.
 void light_distribution(const HostScene& s, int strategy, std::vector<float>* cdf, std::vector<float>* func,
                         float* funcInt);

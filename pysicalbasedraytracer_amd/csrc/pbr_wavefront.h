@@ -517,30 +517,8 @@ __global__ __launch_bounds__(256, REFILL ? PBR_REFILL_OCC : PBR_TRAV_OCC) void k
 }
 
 // One level of WhittedIntegrator::Li for every queued ray (single-light scenes).  LOBES: the lobe
-// kinds present in the scene (kSimpleLobes drops the microfacet code and its registers).
-constexpr int kSimpleLobes = (1 << L_LAMBERT) | (1 << L_OREN) | (1 << L_SPEC_R) | (1 << L_SPEC_T) | (1 << L_FRESNEL_SPEC);
-// Lambert and rough (microfacet) reflection / transmission only — matte, plastic, metal and rough
-// glass: the Path/VolPath shading kernels for C4 and C5 without the specular and Oren-Nayar code
-constexpr int kMicroLobes = (1 << L_LAMBERT) | (1 << L_MF_R) | (1 << L_MF_T);
-// Lambert and perfect mirror reflection only — matte (σ = 0) and mirror materials: C2's dragon and
-// floor, C3's scene
-constexpr int kMatteMirrorLobes = (1 << L_LAMBERT) | (1 << L_SPEC_R);
-// MATS_LDS: the material templates fit kLdsMats and are read from an LDS copy (the BSDF code walks
-// them with dependent loads).
-constexpr int kLdsMats = 32;
-__shared__ MatTemplate s_mats[kLdsMats];
-// The templates a shade kernel reads: the scene's, or the workgroup's LDS copy of them (every thread
-// calls it; the kernel's next barrier publishes the copy).
-template <bool MATS_LDS>
-__device__ __forceinline__ const MatTemplate* stage_mats(const DeviceScene& S) {
-    if constexpr (!MATS_LDS) return S.materials;
-    constexpr int words = (int)(sizeof(MatTemplate) / 4);
-    const int n = 2 * S.nMaterials * words;
-    const uint32_t* src = (const uint32_t*)S.materials;
-    uint32_t* dst = (uint32_t*)s_mats;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-    return s_mats;
-}
+// kinds present in the scene (pbr_lobe_masks.h).
+#include "pbr_lobe_masks.h"
 
 // Waves per SIMD of the Whitted shade kernel for the simple lobe set (C2).  Measured (C2 ms):
 // round 1 4: 19.97, 3: 20.16, 5: 20.11; round 3 4: 17.91-18.02, 3: 18.64, 5: 18.55.

@@ -168,6 +168,27 @@ def li_pixel(scene, rdesc, x, y, sample):
     return out
 
 
+def bsdf(scene, queries):
+    """The oracle's ComputeBSDF, BSDF::f, Pdf and Sample_f on pbr_hip_bsdf's queries, in its records."""
+    lib = load()
+    d = scene.desc()
+    q = np.ascontiguousarray(queries, dtype=capi.bsdf_query_dtype()).reshape(-1)
+    out = np.zeros(q.shape[0], dtype=capi.bsdf_record_dtype())
+    lib.oracle_bsdf.argtypes = [C.POINTER(capi.SceneDesc), C.c_int, C.c_void_p, C.c_void_p]
+    assert lib.oracle_bsdf(C.byref(d), q.shape[0], q.ctypes.data, out.ctypes.data) == 0
+    return out
+
+
+def phase_hg(queries):
+    """The oracle's PhaseHG and HGSample on pbr_hip_phase_hg's queries, in its records."""
+    lib = load()
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 9)
+    out = np.zeros((q.shape[0], 5), dtype=np.float32)
+    lib.oracle_phase_hg.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    assert lib.oracle_phase_hg(q.shape[0], capi.fptr(q), capi.fptr(out)) == 0
+    return out
+
+
 def triangle_test(tri, ray):
     lib = load()
     t = np.ascontiguousarray(tri, dtype=np.float32).reshape(9)

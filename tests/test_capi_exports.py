@@ -56,6 +56,10 @@ def test_null_arguments_are_rejected():
     assert lib.pbr_hip_set_profiling(None, 1) == capi.PBR_E_INVALID
     assert lib.pbr_hip_get_profile(None, None, 0, None) == capi.PBR_E_INVALID
     assert lib.pbr_hip_intersect_walk(None, capi.WALK_LANE, 1, None, None, 0, 0, None) == capi.PBR_E_INVALID
+    assert lib.pbr_hip_bsdf(None, capi.BSDF_VARIANT_ALL, 1, None, None) == capi.PBR_E_INVALID
+    assert lib.pbr_hip_bsdf_host(None, capi.BSDF_VARIANT_ALL, 1, None, None) == capi.PBR_E_INVALID
+    assert lib.pbr_hip_phase_hg(None, 1, None, None) == capi.PBR_E_INVALID
+    assert lib.pbr_hip_phase_hg_host(1, None, None) == capi.PBR_E_INVALID
 
 
 def test_release_library_reads_no_environment():
