@@ -192,6 +192,19 @@ __device__ __forceinline__ void get2d(const DeviceSampler& s, SState& st, float*
     *b = sample_dimension<LDS, KIND>(s, st.index, st.sid, st.dim + 1, st.px, st.py);
     st.dim += 2;
 }
+// A Get2D whose values the caller cannot use: only the dimension counter moves, as get2d moves it.
+// Halton and Sobol values lie in [0, 1) and drawing them has no other effect.  A PBR_SAMPLER_TABLE
+// draw reports a table that lacks the dimension (table_dimension), so that sampler still draws.
+template <bool LDS = false, int KIND = -1>
+__device__ __forceinline__ void skip2d(const DeviceSampler& s, SState& st) {
+    if (KIND == PBR_SAMPLER_TABLE || (KIND < 0 && s.type == PBR_SAMPLER_TABLE)) {
+        float a, b;
+        get2d<LDS, KIND>(s, st, &a, &b);
+        return;
+    }
+    if (st.dim == 4) st.dim = 5;
+    st.dim += 2;
+}
 
 // ---------------------------------------------------------------- camera (Perspective.cpp:44-80)
 // PINHOLE: the caller knows lensRadius == 0 (the lens branch is compiled out)
@@ -995,6 +1008,9 @@ struct pbr_hip_ctx {
     bool inFlight = false;
     // wavefront buffers of the two chunk lanes, and the lane-1 stream with its fork/join events
     WfBufs wb[kWfLanes];
+    // each lane's per-pixel table for the fused Whitted level 0 (k_wf_pixel_table): 8 B per pixel of a
+    // chunk, beside the lane buffers and outside their byte count (the plan's estimate is per sample)
+    DevBuf dPixTab[kWfLanes];
     hipStream_t side[kWfLanes] = {};     // lanes 1.. (lane 0: the caller's stream, or ctx->stream — wf_fork)
     hipStream_t lane0 = nullptr;         // lane 0's stream in the current frame or batch (render_impl, wf_fork)
     WfChunks lastPlan = wf_no_chunks();  // what the last render call ran (pbr_hip_last_chunks); lanes 0: the megakernel
@@ -1463,6 +1479,13 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
     // Default: when the frame is one chunk (no lane overlap).  Measured on C2: a 1/8 shard
     // 3.97 → 3.54 ms; the whole frame (two lanes) 23.43 → 23.76 ms, so off there.
     const bool shadowOverlap = ch.lanes == 1 && !F.batch && !ctx->sched.serial && maxLevels <= kWfMaxDepth + 2;
+    // The fused level 0 reads its pixels from a table filled once per chunk (k_wf_pixel_table) when a
+    // wave's 64 samples share a pixel and x | y << 16 holds every pixel of the tiles; else camera_trace
+    // works each sample's pixel out itself.  Filled per chunk, not kept: tiles, raster and sampler may
+    // change from call to call.
+    bool pixTable = PBR_WF_PIXEL_TABLE && fuseCamera && !textured && !ml && spp % 64 == 0;
+    for (size_t t = 0; t + 3 < ctx->tilesHost.size(); t += 4)
+        if (ctx->tilesHost[t + 2] > 65536 || ctx->tilesHost[t + 3] > 65536) pixTable = false;
     WfParams WL[kWfLanes];
     int* cntL[kWfLanes];
     for (int l = 0; l < ch.lanes; ++l) {
@@ -1512,6 +1535,7 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
         // Halton dims one sample reaches: 5 camera + per level 2 per light + 2 (SpecularReflect)
         W.P.smp.ldsDims = std::min(kLdsDims, 5 + (2 * lightsPerShade + 2) * levels + 2);
         W.cap = (int)cap;
+        if (pixTable) HIP_TRY(ctx->dPixTab[l].ensure((size_t)ch.chunkPix * sizeof(uint2)));
     }
     const bool pass = F.accum != nullptr;
     auto queue = [&](int l, int k) {
@@ -1562,6 +1586,8 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
                 else hipLaunchKernelGGL(k_wf_camera_extend<kCameraShort>, dim3((W.nSamples + 255) / 256), blk, 0, st, W));
         }
         prof_host(ctx, KP_WF_CAMERA, 0, (unsigned long long)W.nSamples);
+        uint2* const tab = pixTable ? (uint2*)ctx->dPixTab[l].p : nullptr;   // (k_wf_shade reads it at level 0 only)
+        if (tab) hipLaunchKernelGGL(k_wf_pixel_table, dim3((W.chunkPix + 255) / 256), blk, 0, st, W, tab);
         const hipStream_t sst = shadowOverlap ? ctx->shadowStream[l] : st;
         WfBufs& B = ctx->wb[l];
         for (int level = 0; level < maxLevels; ++level) {
@@ -1581,25 +1607,25 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
             PROF_LAUNCH(kShade, st,
             if (textured) {
                 if (ml) hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes | kTexturedLobes, false>), gstride, blk, 0, st, W, l0);
-                else hipLaunchKernelGGL((k_wf_shade<kAllLobes | kTexturedLobes, false>), gstride, blk, 0, st, W, l0);
+                else hipLaunchKernelGGL((k_wf_shade<kAllLobes | kTexturedLobes, false>), gstride, blk, 0, st, W, l0, tab);
             } else if (ml) {
                 if (simple && matsLds) hipLaunchKernelGGL((k_wf_shade_ml<kSimpleLobes, true>), gstride, blk, 0, st, W, l0);
                 else if (simple) hipLaunchKernelGGL((k_wf_shade_ml<kSimpleLobes, false>), gstride, blk, 0, st, W, l0);
                 else if (matsLds) hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes, true>), gstride, blk, 0, st, W, l0);
                 else hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes, false>), gstride, blk, 0, st, W, l0);
             } else if (fuseCamera && l0 && pass) {   // the fused level 0 of a sample pass
-                if (mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true, true>), gstride, blk, 0, st, W, l0);
-                else if (mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0);
-                else hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0);
-            } else if (fuseCamera && l0 && mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true>), gstride, blk, 0, st, W, l0);
-            else if (fuseCamera && l0 && mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0);
-            else if (fuseCamera && l0) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0);
-            else if (mm && matsLds && skyHalton) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC_MM, false, true>), gstride, blk, 0, st, W, l0);
-            else if (mm && matsLds) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true>), gstride, blk, 0, st, W, l0);
-            else if (simple && matsLds) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true>), gstride, blk, 0, st, W, l0);
-            else if (simple) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, false>), gstride, blk, 0, st, W, l0);
-            else if (matsLds) hipLaunchKernelGGL((k_wf_shade<kAllLobes, true>), gstride, blk, 0, st, W, l0);
-            else hipLaunchKernelGGL((k_wf_shade<kAllLobes, false>), gstride, blk, 0, st, W, l0));
+                if (mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true, true>), gstride, blk, 0, st, W, l0, tab);
+                else if (mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0, tab);
+                else hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0, tab);
+            } else if (fuseCamera && l0 && mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true>), gstride, blk, 0, st, W, l0, tab);
+            else if (fuseCamera && l0 && mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0, tab);
+            else if (fuseCamera && l0) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0, tab);
+            else if (mm && matsLds && skyHalton) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC_MM, false, true>), gstride, blk, 0, st, W, l0, tab);
+            else if (mm && matsLds) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true>), gstride, blk, 0, st, W, l0, tab);
+            else if (simple && matsLds) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true>), gstride, blk, 0, st, W, l0, tab);
+            else if (simple) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, false>), gstride, blk, 0, st, W, l0, tab);
+            else if (matsLds) hipLaunchKernelGGL((k_wf_shade<kAllLobes, true>), gstride, blk, 0, st, W, l0, tab);
+            else hipLaunchKernelGGL((k_wf_shade<kAllLobes, false>), gstride, blk, 0, st, W, l0, tab));
             if (l0) prof_host(ctx, kShade, 0, (unsigned long long)W.nSamples);
             if (l0 && fuseCamera && !textured && !ml) prof_host(ctx, kShade, 6, (unsigned long long)W.nSamples);
             if (int rc = prof_sums(ctx, st, kShade, {l0 ? nullptr : W.cur.segCount, W.shadowSeg, nullptr, nullptr,

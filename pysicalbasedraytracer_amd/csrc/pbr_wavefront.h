@@ -538,22 +538,62 @@ __global__ __launch_bounds__(256, REFILL ? PBR_REFILL_OCC : PBR_TRAV_OCC) void k
 #ifndef PBR_WF_FUSED_MATS_LDS
 #define PBR_WF_FUSED_MATS_LDS 0
 #endif
+// Build switches of the level-0 table and the passed-over SpecularReflect draw (0: the code before
+// them), as built for the A/B sessions of profiles/level0_table_ab.log
+#ifndef PBR_WF_PIXEL_TABLE
+#define PBR_WF_PIXEL_TABLE 1
+#endif
+#ifndef PBR_WF_SKIP_SPEC_DRAW
+#define PBR_WF_SKIP_SPEC_DRAW 1
+#endif
+// What the fused level-0 shade needs of each pixel of the chunk, worked out once per pixel instead
+// of once per sample: one thread per pixel runs pixel_xy and halton_pixel_offset (the same code on
+// the same values as the per-sample path, so the same bits) and leaves 8 bytes.  Launched ahead of
+// the chunk's level-0 shade when a wave's samples share a pixel (spp a multiple of 64) and both
+// raster sides fit 16 bits; at 64 spp that is 1/64 of the evaluations.
+__global__ __launch_bounds__(256) void k_wf_pixel_table(WfParams W, uint2* pixTab) {
+    const int lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lp >= W.chunkPix) return;
+    int x, y;
+    pixel_xy(W.P, W.chunkPix0 + lp, &x, &y);
+    const uint32_t off = W.P.smp.type == PBR_SAMPLER_HALTON ? halton_pixel_offset(hparams(W.P.smp), x, y) : 0u;
+    pixTab[lp] = make_uint2((uint32_t)x | (uint32_t)y << 16, off);
+}
+
 // k_wf_camera_extend's work for queue position q inside the level-0 shade (CAMERA): the camera
 // sample's ray and its closest hit, as the queue entry the shade would have read.  Every lane of
-// the wave calls it (the packet walk is wave-wide); `active` lanes hold a sample.
+// the wave calls it (the packet walk is wave-wide); `active` lanes hold a sample.  pixTab: the
+// chunk's pixels as k_wf_pixel_table left them (x | y << 16, the Halton pixel offset), or null.
 template <bool PINHOLE = false, int KIND = -1, bool PASS = false>
-__device__ __forceinline__ void camera_trace(const WfParams& W, bool active, int q, float4* o, float4* d, float4* hr,
-                                             uint32_t* index) {
+__device__ __forceinline__ void camera_trace(const WfParams& W, const uint2* pixTab, bool active, int q, float4* o, float4* d,
+                                             float4* hr, uint32_t* index) {
     const KParams& P = W.P;
     Ray r;
     r.o = mk(0, 0, 0); r.d = mk(0, 0, 1); r.tMax = 0; r.medium = -1;
     int dim = 0;
     if (active) {
-        const int lp = q / P.spp, s = q - lp * P.spp;
-        int x, y;
-        pixel_xy(P, W.chunkPix0 + lp, &x, &y);
+        int x, y, s;
         SState st;
-        st.index = sample_index<KIND>(P.smp, x, y, PASS ? P.smp.passFirst + s : s).lo;
+        if (pixTab) {
+            // the wave's 64 queue positions start at a multiple of 64 and spp is a multiple of 64: one
+            // pixel, found from the wave's first position and read through a wave-uniform address
+            const uint32_t q0 = (uint32_t)__builtin_amdgcn_readfirstlane(q) & ~63u;
+            const uint32_t lp = q0 / (uint32_t)P.spp;
+            const uint2 e = pixTab[lp];
+            s = q - (int)(lp * (uint32_t)P.spp);
+            x = (int)(e.x & 0xffffu);
+            y = (int)(e.x >> 16);
+            const int sn = PASS ? P.smp.passFirst + s : s;
+            if (KIND == PBR_SAMPLER_HALTON || (KIND < 0 && P.smp.type == PBR_SAMPLER_HALTON))
+                st.index = e.y + (uint32_t)sn * (uint32_t)P.smp.stride;   // sample_index's Halton line
+            else
+                st.index = sample_index<KIND>(P.smp, x, y, sn).lo;
+        } else {
+            const int lp = q / P.spp;
+            s = q - lp * P.spp;
+            pixel_xy(P, W.chunkPix0 + lp, &x, &y);
+            st.index = sample_index<KIND>(P.smp, x, y, PASS ? P.smp.passFirst + s : s).lo;
+        }
         st.sid = s;
         st.dim = 0;
         st.px = x;
@@ -590,7 +630,7 @@ __device__ __forceinline__ void camera_trace(const WfParams& W, bool active, int
 template <int LOBES, bool MATS_LDS,
           int OCC = (LOBES & ~kSimpleLobes) ? 2 : (LOBES == kMatteMirrorLobes ? PBR_WF_SHADE_OCC_MM : PBR_WF_SHADE_OCC),
           bool CAMERA = false, bool SKY = false, bool PASS = false>
-__global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0) {
+__global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, const uint2* pixTab) {
     static_assert(!PASS || CAMERA, "only the fused level-0 shade starts samples");
     static_assert(!SKY || (LOBES & kTexturedLobes) == 0, "the SkyBox variant is untextured");
     constexpr int kSmp = SKY ? PBR_SAMPLER_HALTON : -1;   // the SkyBox variants run Halton frames only
@@ -615,7 +655,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0) {
         f3 skyWi = mk(0, 0, 0);
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f), d = o, hr = o;
         uint32_t camIndex = 0;
-        if constexpr (CAMERA) camera_trace<SKY, kSmp, PASS>(W, active, q, &o, &d, &hr, &camIndex);   // level 0 only
+        if constexpr (CAMERA) camera_trace<SKY, kSmp, PASS>(W, pixTab, active, q, &o, &d, &hr, &camIndex);   // level 0 only
         else if (active) { o = W.cur.o[q]; d = W.cur.d[q]; hr = W.cur.hit[q]; }
         if (active) {
             id = level0 ? q : W.cur.id[q];
@@ -721,9 +761,12 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0) {
                         f3 wi = mk(0, 0, 0);
                         float pdf = 0;
                         int stype = 0;
-                        float a, b;
-                        get2d<true, kSmp>(P.smp, st, &a, &b);
-                        // only L_SPEC_R lobes match BSDF_REFLECTION | BSDF_SPECULAR
+                        float a = 0.f, b = 0.f;
+                        // only L_SPEC_R lobes match BSDF_REFLECTION | BSDF_SPECULAR.  With exactly one,
+                        // Sample_f picks it whatever u0 in [0, 1) is (comp = min(floor(u0·1), 0)) and the
+                        // lobe reads neither value, so the two dimensions are passed over, not drawn
+                        if (PBR_WF_SKIP_SPEC_DRAW && num_components(bsdf, BSDF_REFLECTION | BSDF_SPECULAR) == 1) skip2d<true, kSmp>(P.smp, st);
+                        else get2d<true, kSmp>(P.smp, st, &a, &b);
                         rgb f = bsdf_sample<(1 << L_SPEC_R)>(bsdf, wo, &wi, a, b, &pdf, BSDF_REFLECTION | BSDF_SPECULAR, &stype);
                         if (!black(f) && pdf > 0.f && absdot(wi, isect.sn) != 0.f && depth + 1 < kWfMaxDepth) {
                             W.recF[ri] = make_float4(f.r, f.g, f.b, absdot(wi, isect.sn));
@@ -920,8 +963,10 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade_ml(WfParams W, int level0
                 f3 wi = mk(0, 0, 0);
                 float pdf = 0;
                 int stype = 0;
-                float a, b;
-                get2d<true>(P.smp, st, &a, &b);
+                float a = 0.f, b = 0.f;
+                // one specular reflection lobe: the draw cannot change the result (as k_wf_shade)
+                if (PBR_WF_SKIP_SPEC_DRAW && num_components(bsdf, BSDF_REFLECTION | BSDF_SPECULAR) == 1) skip2d<true>(P.smp, st);
+                else get2d<true>(P.smp, st, &a, &b);
                 rgb f = bsdf_sample<(1 << L_SPEC_R)>(bsdf, isect.wo, &wi, a, b, &pdf, BSDF_REFLECTION | BSDF_SPECULAR, &stype);
                 if (!black(f) && pdf > 0.f && absdot(wi, isect.sn) != 0.f && depth + 1 < kWfMaxDepth) {
                     W.recF[ri] = make_float4(f.r, f.g, f.b, absdot(wi, isect.sn));
