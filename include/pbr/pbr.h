@@ -266,7 +266,7 @@ struct TriangleMesh {   // Shape/Triangle.h:11-24; vertices kept in object space
     Transform objectToWorld;
     std::vector<int> vertexIndices;
     std::vector<float> p;    // 3 per vertex
-    std::vector<float> n;    // 3 per vertex or empty
+    std::vector<float> n;    // 3 per vertex (object space: the triangles are smooth-shaded, Triangle.cpp:186-253) or empty
     std::vector<float> uv;   // 2 per vertex or empty
 };
 class Triangle : public Shape {
@@ -425,9 +425,9 @@ class SurfaceInteraction {
     float time = 0;
     MediumInterface mediumInterface;
     Point2f uv;
-    Vector3f dpdu;
+    Vector3f dpdu;           // (on a mesh with normals: shading.dpdu — the device's record carries one dpdu)
     struct {
-        Normal3f n;
+        Normal3f n;          // the interpolated normal's frame on a mesh with normals, else n
         Vector3f dpdu;
     } shading;
     const Primitive* primitive = nullptr;

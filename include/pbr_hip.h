@@ -118,7 +118,7 @@ typedef struct pbr_shape_desc {
     int n_vertices;
     const int32_t* indices;     /* 3*n_triangles */
     const float* P;             /* 3*n_vertices, object space */
-    const float* N;             /* optional 3*n_vertices per-vertex normals, or NULL */
+    const float* N;             /* optional 3*n_vertices per-vertex normals (object space), or NULL */
     const float* UV;            /* optional 2*n_vertices, or NULL (default (0,0),(1,0),(1,1)) */
     /* sphere (Shape/Sphere.h) */
     float radius;
@@ -636,8 +636,9 @@ typedef struct pbr_surface_hit {
     float t;
     float b[3];                 /* barycentrics of the watertight test (triangles; 0 for spheres) */
     float p[3], p_error[3];
-    float n[3];                 /* geometric normal (Triangle.cpp:197-206 orientation rules) */
-    float ns[3], dpdu[3];       /* shading frame after the per-vertex normals */
+    float n[3];                 /* geometric normal (Triangle.cpp:182-184 orientation rules; on a mesh with
+                                 * normals turned to ns's side, Interaction.cpp:104-105) */
+    float ns[3], dpdu[3];       /* shading frame after the per-vertex normals (Triangle.cpp:186-253) */
     float wo[3];
     float uv[2];                /* surface (u, v) of the hit (Triangle.cpp:160-190; sphere: phi/phiMax, (theta-thetaMin)/range) */
     int medium_inside, medium_outside;   /* the primitive's MediumInterface (indices, -1 = none) */
@@ -724,6 +725,24 @@ int pbr_hip_bsdf_host(const pbr_material_desc* material, int variant, int n, con
  * value (5 floats).  The _host form runs the same source on the CPU. */
 int pbr_hip_phase_hg(pbr_hip_ctx* ctx, int n, const float* queries, float* out);
 int pbr_hip_phase_hg_host(int n, const float* queries, float* out);
+
+/* ---- The shading frame of a triangle with per-vertex normals (Shape/Triangle.cpp:148-253,
+ * SurfaceInteraction::SetShadingGeometry, Core/Interaction.cpp:98-113) on caller-given triangles: the
+ * function the hit path calls (csrc/pbr_shading_frame.h), compiled for the host.  No context, no GPU.
+ * p and n are world space: n as the TriangleMesh constructor leaves the normals (the inverse
+ * transpose applied, not renormalised).  out: 9 floats per query, n.xyz, shading.n.xyz,
+ * shading.dpdu.xyz. */
+typedef struct pbr_shading_query {
+    float p[9];                 /* the three vertices */
+    float n[9];                 /* their normals */
+    float uv[6];                /* their UVs; read only when has_uv != 0 */
+    float b[3];                 /* the hit's barycentrics */
+    int has_uv;                 /* 0: Triangle::GetUVs' default (0,0) (1,0) (1,1) */
+    int reverse_orientation;    /* the shape's own flag: flips ts */
+    int swaps_handedness;       /* of the shape's transform: with the flag above, flips the geometric normal */
+    int pad[2];
+} pbr_shading_query;            /* 32 words */
+int pbr_hip_shading_host(int n, const pbr_shading_query* queries, float* out);
 
 /* ---- BVH construction (BVHAccel::BVHAccel, Accelerator/BVHAccel.cpp:57-87; SAH recursiveBuild
  * :97-260; flattenBVHTree :262-283) ----

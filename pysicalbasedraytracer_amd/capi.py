@@ -351,8 +351,28 @@ def phase_hg_host(queries, lib=None):
     return out
 
 
+def shading_query_dtype():
+    """pbr_shading_query as a numpy record type (128 bytes)."""
+    import numpy as np
+    return np.dtype([("p", "f4", (3, 3)), ("n", "f4", (3, 3)), ("uv", "f4", (3, 2)), ("b", "f4", 3), ("has_uv", "i4"),
+                     ("reverse_orientation", "i4"), ("swaps_handedness", "i4"), ("pad", "i4", 2)])
+
+
+def shading_host(queries, lib=None):
+    """pbr_hip_shading_host: the hit path's shading frame of a triangle with per-vertex normals,
+    compiled for the CPU.  queries: shading_query_dtype records; returns [n, 3, 3] float32
+    (n, shading.n, shading.dpdu)."""
+    import numpy as np
+    q = np.ascontiguousarray(queries, dtype=shading_query_dtype()).reshape(-1)
+    out = np.zeros((q.shape[0], 3, 3), dtype=np.float32)
+    if (lib or load_library()).pbr_hip_shading_host(q.shape[0], q.ctypes.data, out.ctypes.data) != PBR_OK:
+        raise ValueError("shading_host: refused")
+    return out
+
+
 # Every symbol include/pbr_hip.h declares, with its ctypes signature.
 EXPORTS = {
+    "pbr_hip_shading_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
     "pbr_hip_bsdf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pbr_hip_bsdf_host": (C.c_int, [C.POINTER(MaterialDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pbr_hip_phase_hg": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
@@ -424,7 +444,7 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk",
                    "pbr_hip_plan_chunks", "pbr_hip_last_chunks", "pbr_hip_adaptive_select", "pbr_hip_render_passes_list",
                    "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov", "pbr_hip_denoise", "pbr_hip_bsdf",
-                   "pbr_hip_bsdf_host", "pbr_hip_phase_hg", "pbr_hip_phase_hg_host")
+                   "pbr_hip_bsdf_host", "pbr_hip_phase_hg", "pbr_hip_phase_hg_host", "pbr_hip_shading_host")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

@@ -51,7 +51,7 @@ constexpr int kAovOcc = 5;
 
 // TEX: the scene has image textures (else their evaluation is compiled out, as make_bsdf<TEX>);
 // BINARY: the scene runs the per-lane binary walk (DeviceScene::binaryWalk), whose stack is scratch
-template <bool TEX, bool BINARY>
+template <bool NRM, bool TEX, bool BINARY>
 __global__ __launch_bounds__(256, kAovOcc) void k_aov(AovParams A) {
     __shared__ float tile[kAovChannels * kAovPitch];
     __shared__ float sums[kAovChannels * kAovBlock];
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256, kAovOcc) void k_aov(AovParams A) {
                             hit = false;
                         } else {
                             Isect cross;
-                            hit_isect(S, h, r, &cross);
+                            hit_isect<NRM>(S, h, r, &cross);
                             tsum = tsum + r.tMax;
                             r = spawn_ray(cross, r.d);
                             again = true;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256, kAovOcc) void k_aov(AovParams A) {
         float t = 0.f;
         if (hit) {
             Isect si;
-            hit_isect(S, h, r, &si);
+            hit_isect<NRM>(S, h, r, &si);
             const float4 a = A.albedo[mat];
             alb[0] = a.x; alb[1] = a.y; alb[2] = a.z;
             if constexpr (TEX) {

@@ -6,6 +6,7 @@
 #include "pbr_layout.h"
 #include "pbr_material.h"
 #include "pbr_math.h"
+#include "pbr_shading_frame.h"
 
 namespace pbr {
 
@@ -144,12 +145,31 @@ __device__ __forceinline__ void trav_diag(unsigned long long* prof, int kind, co
 #endif
 }
 
-// Triangle::Intersect's SurfaceInteraction (Triangle.cpp:148-246), no shading normals
+// The shading frame of a PRIM_HAS_N slot from the three normals of its triN record, and the normal
+// Triangle::Sample gives a point of such a light (pbr_shading_frame.h).  Out of line, by value, as
+// inf_sample_li is: inlined, the frame's three fp64 crosses raised the register need of every kernel
+// that builds an interaction, whether its scene has normals or not (Whitted's level-0 shade and the
+// feature kernel began to spill, two VolPath shades lost a wave or went to 1.2 KB of scratch:
+// profiles/shading_normals.md).  The call alone still cost Whitted's level-0 shade two spilled registers,
+// so the wavefront shade kernels and the feature kernel are compiled twice: NRM = false, launched for scenes without normals,
+// is the code they were before (triangle_si, hit_isect, sample_li and pdf_li compile the branch out).
+__device__ __noinline__ ShadingFrame triangle_normals_frame(const float4* tn, float b0, float b1, float b2, f3 n, f3 dpdu,
+                                                            bool reverse) {
+    const float4 a = tn[0], b = tn[1], c = tn[2];
+    return shading_frame(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), b0, b1, b2, n, dpdu, reverse);
+}
+__device__ __noinline__ f3 triangle_sampled_normal(const float4* tn, float b0, float b1, f3 n) {
+    const float4 a = tn[0], b = tn[1], c = tn[2];
+    return sampled_normal(mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), mk(c.x, c.y, c.z), b0, b1, n);
+}
+
+// Triangle::Intersect's SurfaceInteraction (Triangle.cpp:148-253)
 // Hit-record and light-sampling helpers are inlined into the kernels: as calls, every live register
 // of the shading kernels was saved to scratch around them (C5 1757 -> 1701 ms, bit-identical).
 #ifndef PBR_HELPER
 #define PBR_HELPER __device__ __forceinline__
 #endif
+template <bool NRM = true>
 PBR_HELPER void triangle_si(const DeviceScene& S, int slot, const Ray& ray, float b0, float b1, float b2, int flags, Isect* si) {
     const float4* tv = S.triVerts + 3 * (size_t)slot;
     float4 v0 = tv[0], v1 = tv[1], v2 = tv[2];
@@ -176,8 +196,13 @@ PBR_HELPER void triangle_si(const DeviceScene& S, int slot, const Ray& ray, floa
     si->wo = normalize(-ray.d);
     f3 n = normalize(cross(dp02, dp12));
     if (flags & PRIM_FLIP) n = -n;
+    f3 sn = n;
+    if (NRM && (flags & PRIM_HAS_N)) {
+        const ShadingFrame fr = triangle_normals_frame(S.triN + 3 * (size_t)slot, b0, b1, b2, n, dpdu, (flags & PRIM_REVERSE) != 0);
+        n = fr.n; sn = fr.sn; dpdu = fr.dpdu;
+    }
     si->n = n;
-    si->sn = n;
+    si->sn = sn;
     si->dpdu = dpdu;
     si->u = b0 * u0x + b1 * u1x + b2 * u2x;   // uvHit = b0 * uv[0] + b1 * uv[1] + b2 * uv[2]
     si->v = b0 * u0y + b1 * u1y + b2 * u2y;
@@ -847,10 +872,11 @@ __device__ bool traverse(const DeviceScene& S, Ray& r, HitRec* h, Counters* c) {
 
 // The SurfaceInteraction of a closest hit (sphere or triangle), for the ray whose tMax the walk
 // left at the hit.  The medium interface is not set: set_interface, or none (Path, Whitted).
+template <bool NRM = true>
 __device__ __forceinline__ void hit_isect(const DeviceScene& S, const HitRec& h, const Ray& r, Isect* si) {
     const int flags = __float_as_int(S.triVerts[3 * (size_t)h.slot].w);
     if (flags & PRIM_SPHERE) sphere_si(S.spheres[__float_as_int(S.triVerts[3 * (size_t)h.slot].x)], r, r.tMax, si);
-    else triangle_si(S, h.slot, r, h.b0, h.b1, h.b2, flags, si);
+    else triangle_si<NRM>(S, h.slot, r, h.b0, h.b1, h.b2, flags, si);
     si->slot = h.slot;
 }
 
@@ -1551,6 +1577,7 @@ __device__ __noinline__ InfLiSample inf_sample_li(const InfDev* Ep, float u0, fl
     o.L = inf_lookup(E, d0, d1);
     return o;
 }
+template <bool NRM = true>
 PBR_HELPER rgb sample_li(const DeviceScene& S, const DLight& l, const Isect& ref, float u0, float u1, f3* wi, float* pdf, VisPt* v) {
     if (l.type == LT_POINT) {   // PointLight.cpp:5-15
         f3 pl = mk(l.p[0], l.p[1], l.p[2]);
@@ -1568,7 +1595,9 @@ PBR_HELPER rgb sample_li(const DeviceScene& S, const DLight& l, const Isect& ref
         f3 ip = b0 * p0 + b1 * p1 + (1 - b0 - b1) * p2;
         f3 in = normalize(cross(p1 - p0, p2 - p0));
         int flags = __float_as_int(S.triVerts[3 * (size_t)l.primSlot].w);
-        if (flags & PRIM_FLIP) in = in * -1.f;
+        if (NRM && (flags & PRIM_HAS_N)) {   // Triangle.cpp:372-376: the side of the interpolated normal, not the flag's
+            in = triangle_sampled_normal(S.triN + 3 * (size_t)l.primSlot, b0, b1, in);
+        } else if (flags & PRIM_FLIP) in = in * -1.f;
         f3 pAbs = vabs(b0 * p0) + vabs(b1 * p1) + vabs((1 - b0 - b1) * p2);
         f3 ipErr = gamma_n(6) * pAbs;
         float area = (float)(0.5 * (double)len(cross(p1 - p0, p2 - p0)));
@@ -1603,6 +1632,7 @@ PBR_HELPER rgb sample_li(const DeviceScene& S, const DLight& l, const Isect& ref
     return sky_value(S, l, ul, vl);
 }
 // Shape::Pdf through the light's own triangle (Shape.cpp:31-42); 0 for point and skybox lights
+template <bool NRM = true>
 PBR_HELPER float pdf_li(const DeviceScene& S, const DLight& l, const Isect& ref, f3 wi) {
     if (l.type == LT_INF) return inf_pdf_li(S.inf, wi);
     if (l.type != LT_AREA) return 0;
@@ -1613,7 +1643,7 @@ PBR_HELPER float pdf_li(const DeviceScene& S, const DLight& l, const Isect& ref,
     if (!tri_test(p0, p1, p2, ray, &t, &b0, &b1, &b2)) return 0;
     Isect li;
     int flags = __float_as_int(S.triVerts[3 * (size_t)l.primSlot].w);
-    triangle_si(S, l.primSlot, ray, b0, b1, b2, flags, &li);
+    triangle_si<NRM>(S, l.primSlot, ray, b0, b1, b2, flags, &li);
     float area = (float)(0.5 * (double)len(cross(p1 - p0, p2 - p0)));
     float pdf = len2(ref.p - li.p) / (absdot(li.n, -wi) * area);
     if (is_inf(pdf)) pdf = 0.f;

@@ -988,7 +988,7 @@ struct pbr_hip_ctx {
     DevBuf dTexels, dTextures, dTexMats;   // ImageTextures and the textured materials' parameters
     DevBuf dAlbedo;                        // per material: the feature buffers' albedo (pbr_aov.h)
     DevBuf dDnXV[2], dDnNZ, dDnGB;         // the denoiser's working planes (pbr_denoise.h), 16 B per pixel each
-    DevBuf dNodes, dWide, dQuad, dTri, dInfo, dUV, dSph, dMat, dLights, dEnv, dCdf, dFunc, dMedia;
+    DevBuf dNodes, dWide, dQuad, dTri, dInfo, dUV, dTriN, dSph, dMat, dLights, dEnv, dCdf, dFunc, dMedia;
     DevBuf dPrimes, dRecips, dPrimeSums, dPerms, dPrimIds;
     DevBuf dSobol, dSobolHi, dSobolPix;  // active Sobol nibble tables (index bits 0-31, 32-51), pixel tables
     std::vector<uint32_t> sobolBuiltin;
@@ -1138,6 +1138,7 @@ DeviceScene device_scene(pbr_hip_ctx* ctx) {
     S.guard = (int*)ctx->dGuard.p;
     S.primInfo = (const int4*)ctx->dInfo.p;
     S.triUV = h.triUV.empty() ? nullptr : (const float2*)ctx->dUV.p;
+    S.triN = h.triN.empty() ? nullptr : (const float4*)ctx->dTriN.p;
     S.spheres = (const SphereRec*)ctx->dSph.p;
     S.materials = (const MatTemplate*)ctx->dMat.p;
     S.lights = (const DLight*)ctx->dLights.p;
@@ -1428,6 +1429,15 @@ void prof_host(pbr_hip_ctx* ctx, int kind, int field, unsigned long long v) {
     if (ctx->profCount) ctx->profHost[kind][field] += v;
 }
 // a launch (any statement list) bracketed by the profile events of `kind` on stream ST
+// A wavefront shade kernel, or the feature kernel, for this scene: its NRM = true instantiation when some mesh has per-vertex
+// normals (pbr_device.h triangle_normals_frame), else the one without that code.  TARGS: the kernel's
+// other template arguments, in parentheses.
+#define PBR_UNPAREN(...) __VA_ARGS__
+#define PBR_LAUNCH_NRM(NRM, K, TARGS, ...)                                          \
+    do {                                                                            \
+        if (NRM) hipLaunchKernelGGL((K<true, PBR_UNPAREN TARGS>), __VA_ARGS__);     \
+        else hipLaunchKernelGGL((K<false, PBR_UNPAREN TARGS>), __VA_ARGS__);        \
+    } while (0)
 #define PROF_LAUNCH(KIND, ST, ...)                                                  \
     do {                                                                            \
         int pi_ = -1;                                                               \
@@ -1456,6 +1466,7 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
     const bool mm = (lobes & ~kMatteMirrorLobes) == 0;   // Lambert + mirror only (C2)
     const bool textured = (lobes & kTexturedLobes) != 0;
     const bool matsLds = ctx->host.materials.size() <= (size_t)kLdsMats;   // templates staged in LDS
+    const bool nrm = !ctx->host.triN.empty();   // some mesh has per-vertex normals: the shade kernels' NRM variants
     // chunk size, lanes, queue capacities and the level-0 fusion: pbr_chunk_plan.h
     WfPlanIn in;
     in.integrator = PBR_INTEGRATOR_WHITTED;
@@ -1606,26 +1617,26 @@ int render_wavefront(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, const FrameSet
             const int kShade = l0 && fuseCamera ? KP_WF_SHADE0 : KP_WF_SHADE;   // (the fused level 0: its own family)
             PROF_LAUNCH(kShade, st,
             if (textured) {
-                if (ml) hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes | kTexturedLobes, false>), gstride, blk, 0, st, W, l0);
-                else hipLaunchKernelGGL((k_wf_shade<kAllLobes | kTexturedLobes, false>), gstride, blk, 0, st, W, l0, tab);
+                if (ml) PBR_LAUNCH_NRM(nrm, k_wf_shade_ml, (kAllLobes | kTexturedLobes, false), gstride, blk, 0, st, W, l0);
+                else PBR_LAUNCH_NRM(nrm, k_wf_shade, (kAllLobes | kTexturedLobes, false), gstride, blk, 0, st, W, l0, tab);
             } else if (ml) {
-                if (simple && matsLds) hipLaunchKernelGGL((k_wf_shade_ml<kSimpleLobes, true>), gstride, blk, 0, st, W, l0);
-                else if (simple) hipLaunchKernelGGL((k_wf_shade_ml<kSimpleLobes, false>), gstride, blk, 0, st, W, l0);
-                else if (matsLds) hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes, true>), gstride, blk, 0, st, W, l0);
-                else hipLaunchKernelGGL((k_wf_shade_ml<kAllLobes, false>), gstride, blk, 0, st, W, l0);
+                if (simple && matsLds) PBR_LAUNCH_NRM(nrm, k_wf_shade_ml, (kSimpleLobes, true), gstride, blk, 0, st, W, l0);
+                else if (simple) PBR_LAUNCH_NRM(nrm, k_wf_shade_ml, (kSimpleLobes, false), gstride, blk, 0, st, W, l0);
+                else if (matsLds) PBR_LAUNCH_NRM(nrm, k_wf_shade_ml, (kAllLobes, true), gstride, blk, 0, st, W, l0);
+                else PBR_LAUNCH_NRM(nrm, k_wf_shade_ml, (kAllLobes, false), gstride, blk, 0, st, W, l0);
             } else if (fuseCamera && l0 && pass) {   // the fused level 0 of a sample pass
-                if (mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true, true>), gstride, blk, 0, st, W, l0, tab);
-                else if (mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0, tab);
-                else hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true, false, true>), gstride, blk, 0, st, W, l0, tab);
-            } else if (fuseCamera && l0 && mm && skyHalton && !(P.cam.lensRadius > 0)) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true>), gstride, blk, 0, st, W, l0, tab);
-            else if (fuseCamera && l0 && mm) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0, tab);
-            else if (fuseCamera && l0) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true, PBR_WF_SHADE_OCC, true>), gstride, blk, 0, st, W, l0, tab);
-            else if (mm && matsLds && skyHalton) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true, PBR_WF_SHADE_OCC_MM, false, true>), gstride, blk, 0, st, W, l0, tab);
-            else if (mm && matsLds) hipLaunchKernelGGL((k_wf_shade<kMatteMirrorLobes, true>), gstride, blk, 0, st, W, l0, tab);
-            else if (simple && matsLds) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, true>), gstride, blk, 0, st, W, l0, tab);
-            else if (simple) hipLaunchKernelGGL((k_wf_shade<kSimpleLobes, false>), gstride, blk, 0, st, W, l0, tab);
-            else if (matsLds) hipLaunchKernelGGL((k_wf_shade<kAllLobes, true>), gstride, blk, 0, st, W, l0, tab);
-            else hipLaunchKernelGGL((k_wf_shade<kAllLobes, false>), gstride, blk, 0, st, W, l0, tab));
+                if (mm && skyHalton && !(P.cam.lensRadius > 0)) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true, true), gstride, blk, 0, st, W, l0, tab);
+                else if (mm) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true, false, true), gstride, blk, 0, st, W, l0, tab);
+                else PBR_LAUNCH_NRM(nrm, k_wf_shade, (kSimpleLobes, true, PBR_WF_SHADE_OCC, true, false, true), gstride, blk, 0, st, W, l0, tab);
+            } else if (fuseCamera && l0 && mm && skyHalton && !(P.cam.lensRadius > 0)) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kMatteMirrorLobes, PBR_WF_FUSED_MATS_LDS != 0, PBR_WF_FUSED_OCC, true, true), gstride, blk, 0, st, W, l0, tab);
+            else if (fuseCamera && l0 && mm) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kMatteMirrorLobes, true, PBR_WF_SHADE_OCC, true), gstride, blk, 0, st, W, l0, tab);
+            else if (fuseCamera && l0) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kSimpleLobes, true, PBR_WF_SHADE_OCC, true), gstride, blk, 0, st, W, l0, tab);
+            else if (mm && matsLds && skyHalton) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kMatteMirrorLobes, true, PBR_WF_SHADE_OCC_MM, false, true), gstride, blk, 0, st, W, l0, tab);
+            else if (mm && matsLds) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kMatteMirrorLobes, true), gstride, blk, 0, st, W, l0, tab);
+            else if (simple && matsLds) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kSimpleLobes, true), gstride, blk, 0, st, W, l0, tab);
+            else if (simple) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kSimpleLobes, false), gstride, blk, 0, st, W, l0, tab);
+            else if (matsLds) PBR_LAUNCH_NRM(nrm, k_wf_shade, (kAllLobes, true), gstride, blk, 0, st, W, l0, tab);
+            else PBR_LAUNCH_NRM(nrm, k_wf_shade, (kAllLobes, false), gstride, blk, 0, st, W, l0, tab));
             if (l0) prof_host(ctx, kShade, 0, (unsigned long long)W.nSamples);
             if (l0 && fuseCamera && !textured && !ml) prof_host(ctx, kShade, 6, (unsigned long long)W.nSamples);
             if (int rc = prof_sums(ctx, st, kShade, {l0 ? nullptr : W.cur.segCount, W.shadowSeg, nullptr, nullptr,
@@ -1689,6 +1700,7 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
     const bool mm = (lobes & ~kMatteMirrorLobes) == 0;   // Lambert + mirror only (C3)
     const bool textured = (lobes & kTexturedLobes) != 0;
     const bool matsLds = ctx->host.materials.size() <= (size_t)kLdsMats;   // templates staged in LDS
+    const bool nrm = !ctx->host.triN.empty();   // some mesh has per-vertex normals: the shade kernels' NRM variants
     // The classed Path/VolPath shade (k_wfp_shade / k_wfv_shade CLASSED): with materials of several
     // lobe sets (C4's glass, metal, plastic and matte), one launch per lobe set shades that set's hits
     // with a kernel compiled for it.  A material goes to the first of these sets that holds its lobes;
@@ -1852,46 +1864,46 @@ int render_wavefront_path(pbr_hip_ctx* ctx, KParams& P, hipStream_t s, bool vol,
                     constexpr int H = PBR_SAMPLER_HALTON, O = PBR_WFV_OCC;
                     PROF_LAUNCH(KP_WFV_SHADE, st,
                         switch (passKind[p]) {
-                        case 0: hipLaunchKernelGGL((k_wfv_shade<kPassLobes[0], true, O, H, true>), gshade, blk, 0, st, V, l0, p); break;
-                        case 1: hipLaunchKernelGGL((k_wfv_shade<kPassLobes[1], true, O, H, true>), gshade, blk, 0, st, V, l0, p); break;
-                        case 2: hipLaunchKernelGGL((k_wfv_shade<kPassLobes[2], true, O, H, true>), gshade, blk, 0, st, V, l0, p); break;
-                        case 3: hipLaunchKernelGGL((k_wfv_shade<kPassLobes[3], true, O, H, true>), gshade, blk, 0, st, V, l0, p); break;
-                        case 4: hipLaunchKernelGGL((k_wfv_shade<kPassLobes[4], true, O, H, true>), gshade, blk, 0, st, V, l0, p); break;
-                        default: hipLaunchKernelGGL((k_wfv_shade<0, true, O, H, true>), gshade, blk, 0, st, V, l0, p); break;
+                        case 0: PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kPassLobes[0], true, O, H, true), gshade, blk, 0, st, V, l0, p); break;
+                        case 1: PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kPassLobes[1], true, O, H, true), gshade, blk, 0, st, V, l0, p); break;
+                        case 2: PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kPassLobes[2], true, O, H, true), gshade, blk, 0, st, V, l0, p); break;
+                        case 3: PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kPassLobes[3], true, O, H, true), gshade, blk, 0, st, V, l0, p); break;
+                        case 4: PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kPassLobes[4], true, O, H, true), gshade, blk, 0, st, V, l0, p); break;
+                        default: PBR_LAUNCH_NRM(nrm, k_wfv_shade, (0, true, O, H, true), gshade, blk, 0, st, V, l0, p); break;
                         });
                 }
             } else if (vol) {
                 PROF_LAUNCH(KP_WFV_SHADE, st,
-                    if (textured) hipLaunchKernelGGL((k_wfv_shade<kAllLobes | kTexturedLobes, false>), gshade, blk, 0, st, V, l0, 0);
-                    else if (simple && matsLds) hipLaunchKernelGGL((k_wfv_shade<kSimpleLobes, true>), gshade, blk, 0, st, V, l0, 0);
-                    else if (simple) hipLaunchKernelGGL((k_wfv_shade<kSimpleLobes, false>), gshade, blk, 0, st, V, l0, 0);
-                    else if (micro && matsLds && halton) hipLaunchKernelGGL((k_wfv_shade<kMicroLobes, true, PBR_WFV_OCC, PBR_SAMPLER_HALTON>), gshade, blk, 0, st, V, l0, 0);
-                    else if (micro && matsLds) hipLaunchKernelGGL((k_wfv_shade<kMicroLobes, true>), gshade, blk, 0, st, V, l0, 0);
-                    else if (matsLds) hipLaunchKernelGGL((k_wfv_shade<kAllLobes, true>), gshade, blk, 0, st, V, l0, 0);
-                    else hipLaunchKernelGGL((k_wfv_shade<kAllLobes, false>), gshade, blk, 0, st, V, l0, 0));
+                    if (textured) PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kAllLobes | kTexturedLobes, false), gshade, blk, 0, st, V, l0, 0);
+                    else if (simple && matsLds) PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kSimpleLobes, true), gshade, blk, 0, st, V, l0, 0);
+                    else if (simple) PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kSimpleLobes, false), gshade, blk, 0, st, V, l0, 0);
+                    else if (micro && matsLds && halton) PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kMicroLobes, true, PBR_WFV_OCC, PBR_SAMPLER_HALTON), gshade, blk, 0, st, V, l0, 0);
+                    else if (micro && matsLds) PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kMicroLobes, true), gshade, blk, 0, st, V, l0, 0);
+                    else if (matsLds) PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kAllLobes, true), gshade, blk, 0, st, V, l0, 0);
+                    else PBR_LAUNCH_NRM(nrm, k_wfv_shade, (kAllLobes, false), gshade, blk, 0, st, V, l0, 0));
             } else if (classed) {   // one launch per material pass, each compiled for its lobes
                 for (int p = 0; p < (int)passKind.size(); ++p) {
                     constexpr int H = PBR_SAMPLER_HALTON, O = PBR_WFP_OCC;
                     PROF_LAUNCH(KP_WFP_SHADE, st,
                         switch (passKind[p]) {
-                        case 0: hipLaunchKernelGGL((k_wfp_shade<kPassLobes[0], true, PBR_WFP_OCC_L, H, true>), gshade, blk, 0, st, X, l0, p); break;
-                        case 1: hipLaunchKernelGGL((k_wfp_shade<kPassLobes[1], true, O, H, true>), gshade, blk, 0, st, X, l0, p); break;
-                        case 2: hipLaunchKernelGGL((k_wfp_shade<kPassLobes[2], true, O, H, true>), gshade, blk, 0, st, X, l0, p); break;
-                        case 3: hipLaunchKernelGGL((k_wfp_shade<kPassLobes[3], true, O, H, true>), gshade, blk, 0, st, X, l0, p); break;
-                        default: hipLaunchKernelGGL((k_wfp_shade<kPassLobes[4], true, O, H, true>), gshade, blk, 0, st, X, l0, p); break;
+                        case 0: PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kPassLobes[0], true, PBR_WFP_OCC_L, H, true), gshade, blk, 0, st, X, l0, p); break;
+                        case 1: PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kPassLobes[1], true, O, H, true), gshade, blk, 0, st, X, l0, p); break;
+                        case 2: PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kPassLobes[2], true, O, H, true), gshade, blk, 0, st, X, l0, p); break;
+                        case 3: PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kPassLobes[3], true, O, H, true), gshade, blk, 0, st, X, l0, p); break;
+                        default: PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kPassLobes[4], true, O, H, true), gshade, blk, 0, st, X, l0, p); break;
                         });
                 }
             } else {
                 PROF_LAUNCH(KP_WFP_SHADE, st,
-                    if (textured) hipLaunchKernelGGL((k_wfp_shade<kAllLobes | kTexturedLobes, false>), gshade, blk, 0, st, X, l0, 0);
-                    else if (mm && matsLds && sobol) hipLaunchKernelGGL((k_wfp_shade<kMatteMirrorLobes, true, PBR_WFP_OCC_MM, PBR_SAMPLER_SOBOL>), gshade, blk, 0, st, X, l0, 0);
-                    else if (mm && matsLds) hipLaunchKernelGGL((k_wfp_shade<kMatteMirrorLobes, true>), gshade, blk, 0, st, X, l0, 0);
-                    else if (simple && matsLds) hipLaunchKernelGGL((k_wfp_shade<kSimpleLobes, true>), gshade, blk, 0, st, X, l0, 0);
-                    else if (simple) hipLaunchKernelGGL((k_wfp_shade<kSimpleLobes, false>), gshade, blk, 0, st, X, l0, 0);
-                    else if (micro && matsLds && halton) hipLaunchKernelGGL((k_wfp_shade<kMicroLobes, true, PBR_WFP_OCC, PBR_SAMPLER_HALTON>), gshade, blk, 0, st, X, l0, 0);
-                    else if (micro && matsLds) hipLaunchKernelGGL((k_wfp_shade<kMicroLobes, true>), gshade, blk, 0, st, X, l0, 0);
-                    else if (matsLds) hipLaunchKernelGGL((k_wfp_shade<kAllLobes, true>), gshade, blk, 0, st, X, l0, 0);
-                    else hipLaunchKernelGGL((k_wfp_shade<kAllLobes, false>), gshade, blk, 0, st, X, l0, 0));
+                    if (textured) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kAllLobes | kTexturedLobes, false), gshade, blk, 0, st, X, l0, 0);
+                    else if (mm && matsLds && sobol) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kMatteMirrorLobes, true, PBR_WFP_OCC_MM, PBR_SAMPLER_SOBOL), gshade, blk, 0, st, X, l0, 0);
+                    else if (mm && matsLds) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kMatteMirrorLobes, true), gshade, blk, 0, st, X, l0, 0);
+                    else if (simple && matsLds) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kSimpleLobes, true), gshade, blk, 0, st, X, l0, 0);
+                    else if (simple) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kSimpleLobes, false), gshade, blk, 0, st, X, l0, 0);
+                    else if (micro && matsLds && halton) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kMicroLobes, true, PBR_WFP_OCC, PBR_SAMPLER_HALTON), gshade, blk, 0, st, X, l0, 0);
+                    else if (micro && matsLds) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kMicroLobes, true), gshade, blk, 0, st, X, l0, 0);
+                    else if (matsLds) PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kAllLobes, true), gshade, blk, 0, st, X, l0, 0);
+                    else PBR_LAUNCH_NRM(nrm, k_wfp_shade, (kAllLobes, false), gshade, blk, 0, st, X, l0, 0));
             }
             if (l0) prof_host(ctx, kShade, 0, (unsigned long long)W.nSamples);
             if (int rc = prof_sums(ctx, st, kShade, {l0 ? nullptr : W.cur.segCount, vol ? V.trSeg : W.shadowSeg, X.probeSeg,
@@ -2320,6 +2332,7 @@ int pbr_hip_upload_scene(pbr_hip_ctx* ctx, const pbr_scene_desc* desc) {
     HIP_TRY(ctx->dTri.upload(h.triVerts, ctx->stream));
     HIP_TRY(ctx->dInfo.upload(h.primInfo, ctx->stream));
     HIP_TRY(ctx->dUV.upload(h.triUV, ctx->stream));
+    HIP_TRY(ctx->dTriN.upload(h.triN, ctx->stream));
     HIP_TRY(ctx->dSph.upload(h.spheres, ctx->stream));
     HIP_TRY(ctx->dMat.upload(h.materials, ctx->stream));
     HIP_TRY(ctx->dLights.upload(h.lights, ctx->stream));
@@ -2860,6 +2873,7 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
     A.out = aov_out;
     A.albedo = (const float4*)ctx->dAlbedo.p;
     const bool tex = !ctx->host.texMats.empty(), binary = P.S.binaryWalk != 0;
+    const bool nrm = !ctx->host.triN.empty();   // (NRM: pbr_device.h triangle_normals_frame)
     const int kind = tex ? KP_AOV_TEX : KP_AOV;
     ctx->batchFrames = 0;   // (set when the pass is queued)
     begin_lanes(ctx, s);
@@ -2868,8 +2882,8 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
         A.pixEnd = l.pix0 + l.nPix;
         const dim3 grid((unsigned)((l.nPix + P.ppb - 1) / P.ppb)), blk(kAovBlock);
         PROF_LAUNCH(kind, s,
-            if (tex) { if (binary) hipLaunchKernelGGL((k_aov<true, true>), grid, blk, 0, s, A); else hipLaunchKernelGGL((k_aov<true, false>), grid, blk, 0, s, A); }
-            else { if (binary) hipLaunchKernelGGL((k_aov<false, true>), grid, blk, 0, s, A); else hipLaunchKernelGGL((k_aov<false, false>), grid, blk, 0, s, A); });
+            if (tex) { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (true, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (true, false), grid, blk, 0, s, A); }
+            else { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (false, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (false, false), grid, blk, 0, s, A); });
     }
     HIP_TRY(hipGetLastError());
     prof_host(ctx, kind, 0, (unsigned long long)npx * (unsigned long long)samples);

@@ -7,6 +7,8 @@
 //              (spheres: [0].x holds the sphere index)
 //  primInfo  : int4[nPrims]       {flags, material, areaLight, mediumIn | mediumOut<<16}
 //  triUV     : float2[3*nPrims]   only when some mesh carries UVs
+//  triN      : float4[3*nPrims]   only when some mesh carries normals: the slot's three world-space
+//              vertex normals as the TriangleMesh constructor leaves them (xyz, w unused), 48 B/prim
 //  materials : MatTemplate[2*nMaterials]  BSDF lobe templates for allowMultipleLobes = {false,true}
 //  lights    : DLight[nLights]
 //  env       : float4[w*h]        SkyBox texels with HDRtoLDR(·,0.3) applied once at upload
@@ -17,7 +19,9 @@
 
 namespace pbr {
 
-enum PrimFlags { PRIM_SPHERE = 1, PRIM_FLIP = 2, PRIM_HAS_UV = 4, PRIM_LEAF_END = 8 };
+// PRIM_FLIP is reverseOrientation ^ transformSwapsHandedness (the geometric normal's flip);
+// PRIM_REVERSE is reverseOrientation alone, which flips ts of a PRIM_HAS_N triangle (Triangle.cpp:251).
+enum PrimFlags { PRIM_SPHERE = 1, PRIM_FLIP = 2, PRIM_HAS_UV = 4, PRIM_LEAF_END = 8, PRIM_HAS_N = 16, PRIM_REVERSE = 32 };
 constexpr uint32_t kLeafRef = 0x80000000u;   // traversal child reference: leaf | first slot
 enum LobeKind { L_LAMBERT = 0, L_OREN = 1, L_SPEC_R = 2, L_SPEC_T = 3, L_FRESNEL_SPEC = 4, L_MF_R = 5, L_MF_T = 6 };
 enum FresnelKind { FR_NOOP = 0, FR_DIEL = 1, FR_COND = 2 };
@@ -86,6 +90,7 @@ struct DeviceScene {
     const float4* triVerts;
     const int4* primInfo;
     const float2* triUV;
+    const float4* triN;            // null unless some mesh has normals (then PRIM_HAS_N marks its slots)
     const SphereRec* spheres;
     const MatTemplate* materials;  // [2*m + multiLobe]
     const DLight* lights;

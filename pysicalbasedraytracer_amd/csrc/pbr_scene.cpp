@@ -8,6 +8,7 @@
 // the same std::partition / std::nth_element calls on the same element order, so the layout is
 // identical.
 #include "pbr_scene.h"
+#include "pbr_shading_frame.h"
 #include "pbr_material.h"
 #include "pbr_sobol_jk.h"
 #include "pbr_xform.h"
@@ -455,8 +456,9 @@ void build_host_scene(const pbr_scene_desc* d, HostScene* S, const BvhBuildFn* b
     if (d->n_shapes < 0 || (d->n_shapes > 0 && !d->shapes)) fail("bad shapes");
     *S = HostScene();
     const int ns = d->n_shapes;
-    // 1. world-space vertex bake (TriangleMesh ctor, Triangle.cpp:12-44) + primitive list
+    // 1. world-space vertex and normal bake (TriangleMesh ctor, Triangle.cpp:12-44) + primitive list
     std::vector<std::vector<f3>> world(ns);
+    std::vector<std::vector<f3>> worldN(ns);
     std::vector<PrimRef> prims;
     std::vector<int> firstPrim(ns, 0);
     std::vector<int> flip(ns, 0);
@@ -469,11 +471,19 @@ void build_host_scene(const pbr_scene_desc* d, HostScene* S, const BvhBuildFn* b
         firstPrim[i] = (int)prims.size();
         if (sd.material >= d->n_materials) fail("material index out of range");
         if (sd.type == PBR_SHAPE_TRIANGLE_MESH) {
-            if (sd.N) fail("per-vertex normals are not supported");
             if (sd.n_triangles < 0 || sd.n_vertices < 0 || (sd.n_triangles && (!sd.indices || !sd.P))) fail("bad mesh");
             world[i].resize(sd.n_vertices);
             for (int v = 0; v < sd.n_vertices; ++v)
                 world[i][v] = xf_point(&o2w.a[0][0], mk(sd.P[3 * v], sd.P[3 * v + 1], sd.P[3 * v + 2]));
+            if (sd.N) {   // Transform::operator()(Normal3f), Transform.h:159-164: mInv transposed, not renormalised
+                const float* mi = sd.object_to_world.m_inv;
+                worldN[i].resize(sd.n_vertices);
+                for (int v = 0; v < sd.n_vertices; ++v) {
+                    const float x = sd.N[3 * v], y = sd.N[3 * v + 1], z = sd.N[3 * v + 2];
+                    worldN[i][v] = mk(mi[0] * x + mi[4] * y + mi[8] * z, mi[1] * x + mi[5] * y + mi[9] * z,
+                                      mi[2] * x + mi[6] * y + mi[10] * z);
+                }
+            }
             for (int t = 0; t < sd.n_triangles; ++t) {
                 for (int k = 0; k < 3; ++k) {
                     int vi = sd.indices[3 * t + k];
@@ -533,11 +543,13 @@ void build_host_scene(const pbr_scene_desc* d, HostScene* S, const BvhBuildFn* b
     // 3. primitive payloads in BVH order
     std::vector<int>& slotOf = S->slotOf;
     slotOf.assign(np, -1);
-    bool anyUV = false;
+    bool anyUV = false, anyN = false;
     for (int i = 0; i < ns; ++i) if (d->shapes[i].type == PBR_SHAPE_TRIANGLE_MESH && d->shapes[i].UV) anyUV = true;
+    for (int i = 0; i < ns; ++i) if (d->shapes[i].type == PBR_SHAPE_TRIANGLE_MESH && d->shapes[i].N) anyN = true;
     S->triVerts.assign((size_t)np * 12, 0.f);
     S->primInfo.assign((size_t)np * 4, 0);
     if (anyUV) S->triUV.assign((size_t)np * 6, 0.f);
+    if (anyN) S->triN.assign((size_t)np * 12, 0.f);
     for (int slot = 0; slot < np; ++slot) {
         const PrimRef& p = prims[S->primIds[slot]];
         slotOf[S->primIds[slot]] = slot;
@@ -555,6 +567,15 @@ void build_host_scene(const pbr_scene_desc* d, HostScene* S, const BvhBuildFn* b
                     int vi = sd.indices[3 * p.tri + k];
                     S->triUV[(size_t)slot * 6 + 2 * k] = sd.UV[2 * vi];
                     S->triUV[(size_t)slot * 6 + 2 * k + 1] = sd.UV[2 * vi + 1];
+                }
+            }
+            if (sd.N) {
+                flags |= PRIM_HAS_N;
+                if (sd.reverse_orientation != 0) flags |= PRIM_REVERSE;
+                for (int k = 0; k < 3; ++k) {
+                    const f3 nv = worldN[p.shape][sd.indices[3 * p.tri + k]];
+                    float* tn = &S->triN[(size_t)slot * 12 + 4 * k];
+                    tn[0] = nv.x; tn[1] = nv.y; tn[2] = nv.z;
                 }
             }
         } else {
@@ -882,3 +903,25 @@ void sobol_pixel_tables(const uint32_t* mats, int m, std::vector<uint32_t>* out)
 }
 
 }  // namespace pbr
+
+// pbr_hip_shading_host: shading_frame (pbr_shading_frame.h) on caller-given triangles, on the CPU
+extern "C" int pbr_hip_shading_host(int n, const pbr_shading_query* queries, float* out) {
+    static_assert(sizeof(pbr_shading_query) == 128, "pbr_shading_query is 32 packed words");
+    if (n < 0 || (n > 0 && (!queries || !out))) return PBR_E_INVALID;
+    using namespace pbr;
+    static const float defaultUV[6] = {0, 0, 1, 0, 1, 1};   // Triangle::GetUVs
+    for (int i = 0; i < n; ++i) {
+        const pbr_shading_query& q = queries[i];
+        const f3 p0 = mk(q.p[0], q.p[1], q.p[2]), p1 = mk(q.p[3], q.p[4], q.p[5]), p2 = mk(q.p[6], q.p[7], q.p[8]);
+        const bool reverse = q.reverse_orientation != 0;
+        f3 ng, dpdu;
+        triangle_frame_inputs(p0, p1, p2, q.has_uv ? q.uv : defaultUV, reverse ^ (q.swaps_handedness != 0), &ng, &dpdu);
+        const ShadingFrame f = shading_frame(mk(q.n[0], q.n[1], q.n[2]), mk(q.n[3], q.n[4], q.n[5]), mk(q.n[6], q.n[7], q.n[8]),
+                                             q.b[0], q.b[1], q.b[2], ng, dpdu, reverse);
+        float* o = out + (size_t)9 * i;
+        o[0] = f.n.x; o[1] = f.n.y; o[2] = f.n.z;
+        o[3] = f.sn.x; o[4] = f.sn.y; o[5] = f.sn.z;
+        o[6] = f.dpdu.x; o[7] = f.dpdu.y; o[8] = f.dpdu.z;
+    }
+    return PBR_OK;
+}

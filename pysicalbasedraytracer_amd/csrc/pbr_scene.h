@@ -38,6 +38,7 @@ struct HostScene {
     std::vector<float> triVerts;            // 12 floats per ordered prim
     std::vector<int32_t> primInfo;          // 4 ints per ordered prim
     std::vector<float> triUV;               // 6 floats per ordered prim (if any UVs)
+    std::vector<float> triN;                // 12 floats per ordered prim (if any normals)
     std::vector<SphereRec> spheres;
     std::vector<MatTemplate> materials;     // 2 per material
     std::vector<DLight> lights;

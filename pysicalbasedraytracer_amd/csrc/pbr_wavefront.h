@@ -627,7 +627,7 @@ __device__ __forceinline__ void camera_trace(const WfParams& W, const uint2* pix
 // caller-saved VGPR; around the late call the shade spilled its whole shading state).  The draw is
 // the light loop's own (same dimensions, same sample index), made under the same condition: a
 // material make_bsdf accepts, with a non-specular lobe.
-template <int LOBES, bool MATS_LDS,
+template <bool NRM, int LOBES, bool MATS_LDS,
           int OCC = (LOBES & ~kSimpleLobes) ? 2 : (LOBES == kMatteMirrorLobes ? PBR_WF_SHADE_OCC_MM : PBR_WF_SHADE_OCC),
           bool CAMERA = false, bool SKY = false, bool PASS = false>
 __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, const uint2* pixTab) {
@@ -691,7 +691,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, c
                     }
                 }
                 Isect isect;
-                hit_isect(S, HitRec{slot, hr.y, hr.z, hr.w}, ray, &isect);
+                hit_isect<NRM>(S, HitRec{slot, hr.y, hr.z, hr.w}, ray, &isect);
                 isect.medIn = isect.medOut = -1;
                 BSDF bsdf;
                 MatTemplate texLocal;   // a textured material's per-hit lobes (make_bsdf)
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, c
                                     pushShadow = true;
                                 }
                             } else if constexpr (!SKY) {
-                                Li = sample_li(S, light, isect, a, b, &wi, &pdf, &vis);
+                                Li = sample_li<NRM>(S, light, isect, a, b, &wi, &pdf, &vis);
                                 if (!(black(Li) || pdf == 0)) {
                                     rgb f = bsdf_f<LOBES>(bsdf, wo, wi, BSDF_ALL);
                                     if (!black(f)) {
@@ -863,7 +863,7 @@ __global__ __launch_bounds__(256, PBR_TRAV_OCC) void k_wf_shadow(WfParams W) {
 // whose shadow ray is pushed leaves its contribution in recC and recV = 0, which k_wf_shadow_ml
 // turns to 1 when the ray gets through.  Everything else is k_wf_shade.
 constexpr int kWfMaxLightsML = 8;
-template <int LOBES, bool MATS_LDS, int OCC = (LOBES & ~kSimpleLobes) ? 2 : 3>
+template <bool NRM, int LOBES, bool MATS_LDS, int OCC = (LOBES & ~kSimpleLobes) ? 2 : 3>
 __global__ __launch_bounds__(256, OCC) void k_wf_shade_ml(WfParams W, int level0) {
     const KParams& P = W.P;
     const DeviceScene& S = P.S;
@@ -905,7 +905,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade_ml(WfParams W, int level0
                 for (int k = 0; k < nL; ++k) W.recV[((size_t)depth * nL + k) * W.cap + id] = 0;
                 W.depthOf[id] = depth;
             } else {
-                hit_isect(S, HitRec{slot, hr.y, hr.z, hr.w}, ray, &isect);
+                hit_isect<NRM>(S, HitRec{slot, hr.y, hr.z, hr.w}, ray, &isect);
                 isect.medIn = isect.medOut = -1;
                 if (!make_bsdf<(LOBES & kTexturedLobes) != 0>(S, mats, isect, false, &bsdf, &texLocal)) {
                     cont = spawn_ray(isect, ray.d);        // Li(isect.SpawnRay(ray.d), depth)
@@ -932,7 +932,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade_ml(WfParams W, int level0
                     f3 wi;
                     float pdf;
                     VisPt vis;
-                    rgb Li = sample_li(S, S.lights[k], isect, a, b, &wi, &pdf, &vis);
+                    rgb Li = sample_li<NRM>(S, S.lights[k], isect, a, b, &wi, &pdf, &vis);
                     if (!(black(Li) || pdf == 0)) {
                         rgb f = bsdf_f<LOBES>(bsdf, isect.wo, wi, BSDF_ALL);
                         if (!black(f)) {

@@ -160,7 +160,7 @@ struct DirectRec {
 // can reach the light — a specular sample, or Pdf_Li != 0 — so it is formed only then (the checks
 // are pure, so their order does not change the outcome): most sampled directions miss a small area
 // light and skip the sum over the lobes.
-template <int LOBES>
+template <int LOBES, bool NRM = true>
 __device__ __forceinline__ bool estimate_bsdf_sample(const DeviceScene& S, const DLight& light, const BSDF& bsdf, const Isect& isect,
                                                      float u0, float u1, float lamL, DirectRec* r, Ray* probe) {
     if constexpr ((PBR_DIAG_SHADE & 2) != 0) return false;
@@ -170,7 +170,7 @@ __device__ __forceinline__ bool estimate_bsdf_sample(const DeviceScene& S, const
     BsdfDraw draw;
     if (!bsdf_sample_dir<LOBES>(bsdf, isect.wo, &wi, u0, u1, &r->scatPdf, flagsNS, &stype, &draw, lamL) || !(r->scatPdf > 0)) return false;
     const bool sampledSpecular = (stype & BSDF_SPECULAR) != 0;
-    const float lp = sampledSpecular ? 0.f : ((PBR_DIAG_SHADE & 4) ? 0.5f : pdf_li(S, light, isect, wi));
+    const float lp = sampledSpecular ? 0.f : ((PBR_DIAG_SHADE & 4) ? 0.5f : pdf_li<NRM>(S, light, isect, wi));
     if (!(sampledSpecular || lp != 0)) return false;
     r->fB = bsdf_sample_sum<LOBES>(bsdf, isect.wo, wi, flagsNS, draw) * absdot(wi, isect.sn);
     if (black(r->fB)) return false;
@@ -376,7 +376,7 @@ __device__ __forceinline__ void shade_entries(const WfpParams& X, int* seg0, int
 // one material class with that class's registers, and only pass 0 reads every entry's hit to
 // classify it.  Entries land in the queues in another order, which nothing depends on (records are
 // indexed by sample or by queue position, and every L update keeps its order: this file's header).
-template <int LOBES, bool MATS_LDS, int OCC = PBR_WFP_OCC, int SMP = -1, bool CLASSED = false>
+template <bool NRM, int LOBES, bool MATS_LDS, int OCC = PBR_WFP_OCC, int SMP = -1, bool CLASSED = false>
 __global__ __launch_bounds__(256, OCC) void k_wfp_shade(WfpParams X, int level0, int pass) {
     WfParams& W = X.W;
     const KParams& P = W.P;
@@ -408,7 +408,7 @@ __global__ __launch_bounds__(256, OCC) void k_wfp_shade(WfpParams X, int level0,
                 load_entry(W, q, level0, level0, &e);
                 const bool found = e.hit.slot >= 0;
                 if (found) {
-                    hit_isect(S, e.hit, e.ray, &isect);
+                    hit_isect<NRM>(S, e.hit, e.ray, &isect);
                     isect.medIn = isect.medOut = -1;
                 }
                 add_emission(S, isect, &e);
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(256, OCC) void k_wfp_shade(WfpParams X, int level0,
                             // Lambda(wo) of the microfacet lobes, once for the estimate's two strategies
                             const float lamL = mf_lambda<LOBES>(bsdf, bsdf.to_local(wo));
                             // the light sample: its whole term, weight folded in, waits for the shadow ray
-                            rgb Li = sample_li(S, light, isect, uL0, uL1, &wi, &lightPdf, &vis);
+                            rgb Li = sample_li<NRM>(S, light, isect, uL0, uL1, &wi, &lightPdf, &vis);
                             rec.a = sp(0.f);
                             if (lightPdf > 0 && !black(Li)) {
                                 rgb f;
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(256, OCC) void k_wfp_shade(WfpParams X, int level0,
                                 }
                             }
                             rec.fB = sp(0.f);
-                            if (!delta && estimate_bsdf_sample<LOBES>(S, light, bsdf, isect, uS0, uS1, lamL, &rec, &probe)) {
+                            if (!delta && estimate_bsdf_sample<LOBES, NRM>(S, light, bsdf, isect, uS0, uS1, lamL, &rec, &probe)) {
                                 pushProbe = true;
                                 rec.flags |= kWfpBPending;
                             }

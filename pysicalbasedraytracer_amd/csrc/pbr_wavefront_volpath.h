@@ -42,7 +42,7 @@ __device__ __forceinline__ int entry_pass_vol(const WfpParams& X, int q) {
 // sample, with the phase function in place of the BSDF at a medium event.  The light sample's f,
 // Li, pdf and weight stay apart in the record, because the resolve multiplies Li by the walk's
 // transmittance first.  (Template parameters: documented at k_wfp_shade.)
-template <int LOBES, bool MATS_LDS, int OCC = PBR_WFV_OCC, int SMP = -1, bool CLASSED = false>
+template <bool NRM, int LOBES, bool MATS_LDS, int OCC = PBR_WFV_OCC, int SMP = -1, bool CLASSED = false>
 __global__ __launch_bounds__(256, OCC) void k_wfv_shade(WfvParams V, int level0, int pass) {
     constexpr bool kMediumPass = CLASSED && LOBES == 0;   // pass 0 of the classed shade
     WfpParams& X = V.X;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, OCC) void k_wfv_shade(WfvParams V, int level0,
                 const Ray& ray = e.ray;
                 const bool found = e.hit.slot >= 0;
                 if (found) {
-                    hit_isect(S, e.hit, ray, &isect);
+                    hit_isect<NRM>(S, e.hit, ray, &isect);
                     set_interface(S, &isect, ray.medium);
                 }
                 // HomogeneousMedium::Sample (HomogeneousMedium.cpp:15-45)
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256, OCC) void k_wfv_shade(WfvParams V, int level0,
                         f3 wi = mk(0, 0, 0);
                         // Lambda(wo) of the microfacet lobes, once for the estimate's two strategies
                         const float lamL = mediumEvent ? kNoLambda : mf_lambda<LOBES>(bsdf, bsdf.to_local(isect.wo));
-                        Li = sample_li(S, light, isect, uL0, uL1, &wi, &lightPdf, &vis);
+                        Li = sample_li<NRM>(S, light, isect, uL0, uL1, &wi, &lightPdf, &vis);
                         rec.a = sp(0.f);
                         if (lightPdf > 0 && !black(Li)) {
                             if (!mediumEvent) rec.a = bsdf_f_pdf<LOBES>(bsdf, isect.wo, wi, flagsNS, &rec.scatPdf, lamL) * absdot(wi, isect.sn);
@@ -167,13 +167,13 @@ __global__ __launch_bounds__(256, OCC) void k_wfv_shade(WfvParams V, int level0,
                         }
                         rec.fB = sp(0.f);
                         if (!delta && !mediumEvent) {
-                            pushProbe = estimate_bsdf_sample<LOBES>(S, light, bsdf, isect, uS0, uS1, lamL, &rec, &probe);
+                            pushProbe = estimate_bsdf_sample<LOBES, NRM>(S, light, bsdf, isect, uS0, uS1, lamL, &rec, &probe);
                         } else if (!delta) {   // the phase function's sample: its value is its pdf
                             const float p = hg_sample(g, isect.wo, &wi, uS0, uS1);
                             rec.fB = sp(p);
                             rec.scatPdf = p;
                             if (!black(rec.fB) && p > 0) {
-                                const float lp = pdf_li(S, light, isect, wi);
+                                const float lp = pdf_li<NRM>(S, light, isect, wi);
                                 if (lp != 0) {
                                     float fp = 1 * p, gp = 1 * lp;
                                     rec.weightB = (fp * fp) / (fp * fp + gp * gp);

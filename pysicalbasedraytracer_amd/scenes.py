@@ -91,9 +91,11 @@ def _xf(t):
 
 
 # ----------------------------------------------------------------------------- geometry
-def dragon_standin(n=224, center=(0.0, 0.0, 0.0), radius=1.0):
+def dragon_standin(n=224, center=(0.0, 0.0, 0.0), radius=1.0, normals=False):
     """Deterministic displaced UV sphere, (n+1) latitude rows × n longitudes → 2·n·n triangles
-    (100,352 at n=224), SURVEY §8(d): r = 1 + 0.08·sin7θ·cos9φ + 0.03·sin(31θ+17φ)."""
+    (100,352 at n=224), SURVEY §8(d): r = 1 + 0.08·sin7θ·cos9φ + 0.03·sin(31θ+17φ).
+    normals=True also returns the analytic per-vertex normals (P, I, N): the gradient of
+    |x − center| − r(θ, φ), unit length, float32 (radial on the pole rows, where φ is singular)."""
     rows = n + 1
     th = np.linspace(0.0, math.pi, rows, dtype=np.float64)
     ph = np.linspace(0.0, 2 * math.pi, n + 1, dtype=np.float64)[:-1]
@@ -114,7 +116,22 @@ def dragon_standin(n=224, center=(0.0, 0.0, 0.0), radius=1.0):
     I = np.concatenate(idx, axis=0).astype(np.int32)
     # interleave to keep neighbouring triangles adjacent in prims order
     I = I.reshape(rows - 1, 2, n, 3).transpose(0, 2, 1, 3).reshape(-1, 3)
-    return P, np.ascontiguousarray(I)
+    if not normals:
+        return P, np.ascontiguousarray(I)
+    # ∇(ρ − r(θ, φ)) = ρ̂ − (∂r/∂θ / ρ) θ̂ − (∂r/∂φ / (ρ sinθ)) φ̂ on the surface ρ = r
+    dr_dt = radius * (0.56 * np.cos(7 * T) * np.cos(9 * Pp) + 0.93 * np.cos(31 * T + 17 * Pp))
+    dr_dp = radius * (-0.72 * np.sin(7 * T) * np.sin(9 * Pp) + 0.51 * np.cos(31 * T + 17 * Pp))
+    sin_t = np.sin(T)
+    pole = np.zeros_like(T, dtype=bool)
+    pole[0, :] = pole[-1, :] = True
+    rho_hat = np.stack([sin_t * np.cos(Pp), np.cos(T), sin_t * np.sin(Pp)], axis=-1)
+    th_hat = np.stack([np.cos(T) * np.cos(Pp), -sin_t, np.cos(T) * np.sin(Pp)], axis=-1)
+    ph_hat = np.stack([-np.sin(Pp), np.zeros_like(Pp), np.cos(Pp)], axis=-1)
+    g_t = np.where(pole, 0.0, dr_dt / r)
+    g_p = np.where(pole, 0.0, dr_dp / (r * np.where(pole, 1.0, sin_t)))
+    G = rho_hat - g_t[..., None] * th_hat - g_p[..., None] * ph_hat
+    G /= np.linalg.norm(G, axis=-1, keepdims=True)
+    return P, np.ascontiguousarray(I), np.ascontiguousarray(G.reshape(-1, 3).astype(f32))
 
 
 def quad(y, half, x0=0.0, z0=0.0, flip=False):
@@ -144,8 +161,9 @@ def load_3d(path):
     return V, F
 
 
-def load_ply(path):
-    """Minimal PLY reader (ascii and binary_little_endian; vertex x,y,z + triangle faces)."""
+def load_ply(path, normals=False):
+    """Minimal PLY reader (ascii and binary_little_endian; vertex x,y,z + triangle faces).
+    normals=True returns (V, F, N): the vertices' nx ny nz as float32, None when the file has none."""
     with open(path, "rb") as fh:
         header = []
         while True:
@@ -167,7 +185,7 @@ def load_ply(path):
         tsize = {"char": "b", "uchar": "B", "int8": "b", "uint8": "B", "short": "h", "ushort": "H", "int16": "h",
                  "uint16": "H", "int": "i", "uint": "I", "int32": "i", "uint32": "I", "float": "f", "float32": "f",
                  "double": "d", "float64": "d"}
-        V = F = None
+        V = F = N = None
         if fmt == "ascii":
             body = fh.read().decode("ascii").split()
             pos = 0
@@ -177,6 +195,8 @@ def load_ply(path):
                     arr = np.array(body[pos:pos + k * count], dtype=np.float64).reshape(count, k)
                     names = [p[-1] for p in props]
                     V = arr[:, [names.index("x"), names.index("y"), names.index("z")]].astype(f32)
+                    if all(k in names for k in ("nx", "ny", "nz")):
+                        N = arr[:, [names.index("nx"), names.index("ny"), names.index("nz")]].astype(f32)
                     pos += k * count
                 elif name == "face":
                     faces = []
@@ -192,6 +212,8 @@ def load_ply(path):
                     dt = np.dtype([(p[-1], "<" + tsize[p[0]]) for p in props])
                     arr = np.frombuffer(fh.read(dt.itemsize * count), dtype=dt)
                     V = np.stack([arr["x"], arr["y"], arr["z"]], axis=1).astype(f32)
+                    if all(k in dt.names for k in ("nx", "ny", "nz")):
+                        N = np.stack([arr["nx"], arr["ny"], arr["nz"]], axis=1).astype(f32)
                 elif name == "face":
                     lp = props[0]
                     cnt_fmt, idx_fmt = "<" + tsize[lp[1]], "<" + tsize[lp[2]]
@@ -205,6 +227,8 @@ def load_ply(path):
                     raise ValueError("unsupported PLY element " + name)
         else:
             raise ValueError("unsupported PLY format " + fmt)
+    if normals:
+        return V, F, N
     return V, F
 
 
@@ -358,7 +382,9 @@ class Scene:
 
     # shapes
     def mesh(self, P, I, material, xform=None, reverse=False, area_light_first=-1, uv=None,
-             medium_inside=-1, medium_outside=-1):
+             medium_inside=-1, medium_outside=-1, normals=None):
+        """A TriangleMesh.  normals: optional [n_vertices, 3] object-space per-vertex normals
+        (TriangleMesh's N): the mesh is then smooth-shaded (Triangle.cpp:186-253)."""
         P = np.ascontiguousarray(P, dtype=f32)
         I = np.ascontiguousarray(I, dtype=np.int32)
         s = capi.ShapeDesc(type=capi.SHAPE_TRIANGLE_MESH)
@@ -372,6 +398,12 @@ class Scene:
             uv = np.ascontiguousarray(uv, dtype=f32)
             s.UV = capi.fptr(uv)
             self._keep.append(uv)
+        if normals is not None:
+            normals = np.ascontiguousarray(normals, dtype=f32)
+            if normals.shape != P.shape:
+                raise ValueError("normals: one (x, y, z) per vertex")
+            s.N = capi.fptr(normals)
+            self._keep.append(normals)
         s.material = material
         s.area_light_first = area_light_first
         s.medium_inside, s.medium_outside = medium_inside, medium_outside
@@ -398,10 +430,10 @@ class Scene:
         self.lights.append(l)
         return len(self.lights) - 1
 
-    def area_light_mesh(self, P, I, Le, material, n_samples=1, two_sided=False, xform=None):
+    def area_light_mesh(self, P, I, Le, material, n_samples=1, two_sided=False, xform=None, normals=None, reverse=False):
         """One DiffuseAreaLight per triangle, pushed in order (main.cpp:367-375)."""
         first = len(self.lights)
-        shape = self.mesh(P, I, material, xform=xform, area_light_first=first)
+        shape = self.mesh(P, I, material, xform=xform, area_light_first=first, normals=normals, reverse=reverse)
         for t in range(np.asarray(I).shape[0]):
             l = capi.LightDesc(type=capi.LIGHT_DIFFUSE_AREA, shape=shape, triangle=t, two_sided=int(two_sided),
                                n_samples=n_samples, medium_inside=-1, medium_outside=-1)
