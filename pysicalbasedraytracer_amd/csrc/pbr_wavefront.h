@@ -32,7 +32,10 @@ static_assert(kWfBlocks == kWfPlanBlocks, "pbr_chunk_plan.h sizes the queue segm
 // Per-kernel profile (pbr_hip_set_profiling): kernel families and their work counters
 // [kind * kProfFields + field].  Field 0 counts the units a family processed, fields 1..4 the
 // entries it pushed (or, for the any-hit kernels, the rays that got through), field 5 the units
-// read from a segmented queue (beyond level 0: one more 4-B id each).
+// read from a segmented queue (beyond level 0: one more 4-B id each).  KP_WF_SHADE0's field 2: the
+// continuation rays the fused level 0 traced in place (its bounce loop) instead of pushing them —
+// field 4 counts only the pushes, so the two add up to the continuations of the unfused level 0
+// and of the levels its in-place trips stand for.
 enum ProfKind {
     KP_WF_CAMERA, KP_WF_SHADE, KP_WF_SHADOW, KP_WF_EXTEND, KP_WF_FINISH,
     KP_WFP_CAMERA, KP_WFP_SHADE, KP_WFP_SHADOW, KP_WFP_PROBE, KP_WFP_RESOLVE, KP_WFP_FINISH,
@@ -546,6 +549,38 @@ __global__ __launch_bounds__(256, REFILL ? PBR_REFILL_OCC : PBR_TRAV_OCC) void k
 #ifndef PBR_WF_SKIP_SPEC_DRAW
 #define PBR_WF_SKIP_SPEC_DRAW 1
 #endif
+// The fused level-0 shade traces whole-wave SpecularReflect continuations itself (the bounce loop of
+// k_wf_shade) instead of queueing them: 0 compiles the code before it.  PBR_WF_INPLACE_MIN: the
+// lanes of a wave that must hold a continuation for the wave to go round (64: whole waves only).
+#ifndef PBR_WF_INPLACE
+#define PBR_WF_INPLACE 1
+#endif
+#ifndef PBR_WF_INPLACE_MIN
+#define PBR_WF_INPLACE_MIN 64
+#endif
+// PBR_WF_INPLACE_ROUNDS: how many levels a wave may trace in place before its continuations go to
+// the queue after all (kWfMaxDepth: no limit of its own).  On C2 about 95% of the level-1 rays
+// miss, so nearly all of the round trips saved are the first level's; deeper chains (facing
+// mirrors) return to the queue, where the level >= 1 shade and the extend kernel keep running —
+// and keep being tested — on deep rays.
+#ifndef PBR_WF_INPLACE_ROUNDS
+#define PBR_WF_INPLACE_ROUNDS 2
+#endif
+constexpr int kWfInplaceMin = PBR_WF_INPLACE_MIN;
+constexpr int kWfInplaceRounds = PBR_WF_INPLACE_ROUNDS;
+static_assert(kWfInplaceRounds >= 1 && kWfInplaceRounds <= kWfMaxDepth, "in-place levels of the wavefront schedule");
+static_assert(kWfInplaceMin >= 1 && kWfInplaceMin <= 64, "in-place threshold: lanes of a 64-wide wave");
+// What a sample of the fused level-0 shade keeps between the trips of its bounce loop: the ray the
+// next trip walks, the sample's Halton index and the sampler dimension reached.  The sample's id is
+// its position in the dense level-0 queue, and the level is the trip's number, the same for every
+// live lane of the wave (each went through SpecularReflect once per trip): it is kept wave-uniform.
+struct WfBounce {
+    Ray ray;
+    int dim;
+    uint32_t index;
+    bool live;   // the lane holds a ray for the next trip
+    int depth;   // wave-uniform
+};
 // What the fused level-0 shade needs of each pixel of the chunk, worked out once per pixel instead
 // of once per sample: one thread per pixel runs pixel_xy and halton_pixel_offset (the same code on
 // the same values as the per-sample path, so the same bits) and leaves 8 bytes.  Launched ahead of
@@ -560,13 +595,14 @@ __global__ __launch_bounds__(256) void k_wf_pixel_table(WfParams W, uint2* pixTa
     pixTab[lp] = make_uint2((uint32_t)x | (uint32_t)y << 16, off);
 }
 
-// k_wf_camera_extend's work for queue position q inside the level-0 shade (CAMERA): the camera
-// sample's ray and its closest hit, as the queue entry the shade would have read.  Every lane of
-// the wave calls it (the packet walk is wave-wide); `active` lanes hold a sample.  pixTab: the
-// chunk's pixels as k_wf_pixel_table left them (x | y << 16, the Halton pixel offset), or null.
+// k_wf_camera_extend's ray set-up for queue position q inside the level-0 shade (CAMERA): the camera
+// sample's ray, the sampler dimension after it and the sample's index.  The shade walks the ray
+// itself (traverse_wave, wave-wide), so every lane of the wave calls this; `active` lanes hold a
+// sample, the others get a ray the walk ignores.  pixTab: the chunk's pixels as k_wf_pixel_table
+// left them (x | y << 16, the Halton pixel offset), or null.
 template <bool PINHOLE = false, int KIND = -1, bool PASS = false>
-__device__ __forceinline__ void camera_trace(const WfParams& W, const uint2* pixTab, bool active, int q, float4* o, float4* d,
-                                             float4* hr, uint32_t* index) {
+__device__ __forceinline__ void camera_ray(const WfParams& W, const uint2* pixTab, bool active, int q, Ray* ray, int* dimOut,
+                                           uint32_t* index) {
     const KParams& P = W.P;
     Ray r;
     r.o = mk(0, 0, 0); r.d = mk(0, 0, 1); r.tMax = 0; r.medium = -1;
@@ -607,12 +643,8 @@ __device__ __forceinline__ void camera_trace(const WfParams& W, const uint2* pix
             W.recA[q] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    HitRec h;
-    h.slot = -1; h.b0 = h.b1 = h.b2 = 0.f;
-    const bool hit = traverse_wave<false>(P.S, r, &h, active);
-    *o = make_float4(r.o.x, r.o.y, r.o.z, r.tMax);
-    *d = make_float4(r.d.x, r.d.y, r.d.z, __int_as_float(pack_dd(dim, 0)));
-    *hr = make_float4(__int_as_float(hit ? h.slot : -1), h.b0, h.b1, h.b2);
+    *ray = r;
+    *dimOut = dim;
 }
 
 // CAMERA (level 0 only): the shade generates and traces its camera rays itself — the camera
@@ -645,27 +677,45 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, c
     const int stride = gridDim.x * blockDim.x;
     const int nIter = (n + stride - 1) / stride;   // <= segCap / 256: a segment holds all pushes
     const int base = wf_block() * W.segCap, sbase = wf_block() * W.shadowSegCap;
-    // one queued ray (a lambda: its registers are allocated apart from the loop's, as k_wfp_shade's)
-    auto shade = [&](const bool active, const int q) {
-        bool pushShadow = false, pushNext = false;
-        int id = 0, depth = 0, dim = 0, emitDepth = 0;
+    // one trip of one queued ray (a lambda: its registers are allocated apart from the loop's, as
+    // k_wfp_shade's).  CAMERA: b.ray is walked here — the camera ray, or on a later trip over the
+    // same samples (the loop below) the continuation the trip before left; returns whether the wave
+    // goes round again.
+    auto shade = [&](WfBounce& b, const int q) -> bool {
+        const bool active = b.live;
+        bool pushShadow = false, pushNext = false, specNext = false;
+        int id = CAMERA ? q : 0, depth = CAMERA ? b.depth : 0, dim = CAMERA ? b.dim : 0, emitDepth = 0;
         Ray ray, shadow, cont;
         rgb contrib = sp(0.f);
         float skyCos = 0.f;
         f3 skyWi = mk(0, 0, 0);
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f), d = o, hr = o;
-        uint32_t camIndex = 0;
-        if constexpr (CAMERA) camera_trace<SKY, kSmp, PASS>(W, pixTab, active, q, &o, &d, &hr, &camIndex);   // level 0 only
-        else if (active) { o = W.cur.o[q]; d = W.cur.d[q]; hr = W.cur.hit[q]; }
+        float4 hr = make_float4(0.f, 0.f, 0.f, 0.f);
+        const uint32_t camIndex = b.index;
+        if constexpr (CAMERA) {   // the kernel's one packet walk (wave-wide: every lane is here)
+            HitRec h;
+            h.slot = -1; h.b0 = h.b1 = h.b2 = 0.f;
+            ray = b.ray;
+            ray.medium = -1;
+            const bool hit = traverse_wave<false>(S, ray, &h, active);
+            hr = make_float4(__int_as_float(hit ? h.slot : -1), h.b0, h.b1, h.b2);
+        }
         if (active) {
-            id = level0 ? q : W.cur.id[q];
-            int dd = __float_as_int(d.w);
-            dim = dd & 0xffff;
-            depth = dd >> 16;
+            if constexpr (!CAMERA) {
+                const float4 o = W.cur.o[q], d = W.cur.d[q];
+                hr = W.cur.hit[q];
+                id = level0 ? q : W.cur.id[q];
+                const int dd = __float_as_int(d.w);
+                dim = dd & 0xffff;
+                depth = dd >> 16;
+                ray = mkray(mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), o.w, -1);
+            }
             emitDepth = depth;
-            ray = mkray(mk(o.x, o.y, o.z), mk(d.x, d.y, d.z), o.w, -1);
             int slot = __float_as_int(hr.x);
-            size_t ri = (size_t)depth * W.cap + id;
+            // (CAMERA: the level is wave-uniform, so the level's offset into the records stays scalar)
+            float4* const recA = W.recA + (CAMERA ? (size_t)b.depth * W.cap : 0);
+            float4* const recF = W.recF + (CAMERA ? (size_t)b.depth * W.cap : 0);
+            float* const recP = W.recP + (CAMERA ? (size_t)b.depth * W.cap : 0);
+            const size_t ri = CAMERA ? (size_t)id : (size_t)depth * W.cap + id;
             if (slot < 0) {   // miss: Σ over all lights of Le (F4)
                 rgb L = sp(0.f);
                 if constexpr (SKY) {   // light_Le's SkyBox branch
@@ -675,7 +725,7 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, c
                     L = L + (light.envW > 0 ? sky_value(S, light, u, v) : sp(0.f));
                 }
                 else for (int i = 0; i < S.nLights; ++i) L = L + light_Le(S, S.lights[i], ray);
-                W.recA[ri] = make_float4(L.r, L.g, L.b, 0.f);
+                recA[ri] = make_float4(L.r, L.g, L.b, 0.f);
                 W.depthOf[id] = depth;
             } else {
                 f3 skyDir = mk(0, 0, 0);
@@ -769,17 +819,18 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, c
                         else get2d<true, kSmp>(P.smp, st, &a, &b);
                         rgb f = bsdf_sample<(1 << L_SPEC_R)>(bsdf, wo, &wi, a, b, &pdf, BSDF_REFLECTION | BSDF_SPECULAR, &stype);
                         if (!black(f) && pdf > 0.f && absdot(wi, isect.sn) != 0.f && depth + 1 < kWfMaxDepth) {
-                            W.recF[ri] = make_float4(f.r, f.g, f.b, absdot(wi, isect.sn));
-                            W.recP[ri] = pdf;
+                            recF[ri] = make_float4(f.r, f.g, f.b, absdot(wi, isect.sn));
+                            recP[ri] = pdf;
                             cont = spawn_ray(isect, wi);
                             pushNext = true;
+                            specNext = true;
                             final_ = false;
                             depth += 1;
                         } else {
                             flagsA = 1.f;   // L += Spectrum(0) from a failed SpecularReflect
                         }
                     }
-                    W.recA[ri] = make_float4(L.r, L.g, L.b, flagsA);
+                    recA[ri] = make_float4(L.r, L.g, L.b, flagsA);
                     if (final_) W.depthOf[id] = depth;
                     dim = st.dim;
                 }
@@ -793,18 +844,59 @@ __global__ __launch_bounds__(256, OCC) void k_wf_shade(WfParams W, int level0, c
             W.sid[si] = id;
             if (W.skyDeferred) W.sw[si] = make_float4(skyWi.x, skyWi.y, skyWi.z, 0.f);
         }
+        bool again = false;
+        if constexpr (CAMERA && PBR_WF_INPLACE) {   // wave-uniform: see the bounce loop below
+            again = b.depth < kWfInplaceRounds && __ballot(pushShadow) == 0ull && __popcll(__ballot(specNext)) >= kWfInplaceMin;
+            if (again) {
+                if (W.prof) prof_count(W.prof + KP_WF_SHADE0 * kProfFields + 2, specNext);
+                b.live = specNext;
+                b.ray = specNext ? cont : mkray(mk(0, 0, 0), mk(0, 0, 1), 0.f, -1);   // (or a ray the walk ignores)
+                b.dim = dim;
+                b.depth += 1;   // = depth of the lanes that stay live
+                pushNext = pushNext && !specNext;   // (a pass-through lane's ray still goes to the queue)
+            }
+        }
         int ni = base + wave_push(&s_push[1], pushNext);
         if (pushNext) {
             W.next.o[ni] = make_float4(cont.o.x, cont.o.y, cont.o.z, cont.tMax);
             W.next.d[ni] = make_float4(cont.d.x, cont.d.y, cont.d.z, __int_as_float(pack_dd(dim, depth)));
             W.next.id[ni] = id;
         }
+        return again;
     };
-    for (int it = 0; it < nIter; ++it) {   // uniform trip count: wave_push needs convergent lanes
+    // The bounce loop (PBR_WF_INPLACE): `again` keeps a wave of the fused level 0 on the samples of
+    // its trip.  Such a wave holds (mostly) one pixel's samples, and on a mirror all of them continue:
+    // instead of a round trip through W.next, the extend kernel and the next level's shade, the wave
+    // walks its continuations here, as the packet it already is, and shades them with the code
+    // above.  It goes round when at least kWfInplaceMin lanes hold a SpecularReflect continuation, no
+    // lane pushed a shadow entry in this trip and it has gone round fewer than kWfInplaceRounds times
+    // (then the continuations are queued after all); lanes without a continuation are not live in
+    // the next walk (their records are final).  What keeps frames bit-identical and the buffers in bounds:
+    //   * a trip writes the records a queued ray of that depth writes, with the same values at the
+    //     same [depth * cap + id] (recA, recF, recP, depthOf): the same code on the same ray, whose
+    //     walk is the lane's own traversal in any packet (traverse_wave);
+    //   * at a given depth a sample is shaded here or from the queue, never both: a lane that goes
+    //     round pushes no continuation, and one that pushes is live no more;
+    //   * a shadow push ends the wave's rounds, so over them a lane pushes at most one shadow entry,
+    //     and at most one continuation (in its last live trip): segCap and shadowSegCap hold as for
+    //     one trip per `it`.  The rounds end at maxDepth / kWfMaxDepth at the latest (specNext);
+    //   * a shadow entry of a later round carries that round's depth (sd.w) in the level-0 shadow
+    //     queue, and the level-0 k_wf_shadow launch, which follows this kernel, adds it there;
+    //   * sampleIndex[q] is still stored (camera_ray): a queued continuation reads it.
+    // (One loop, not a loop per sample inside this one: that form spilled more of the level-0 kernels.)
+    WfBounce b;
+    bool again = false;   // wave-uniform
+    for (int it = 0; it < nIter; it += again ? 0 : 1) {   // uniform trip count: wave_push needs convergent lanes
         const int i = it * stride + wf_block() * blockDim.x + threadIdx.x;
         const bool active = i < n;
         const int q = level0 ? i : seg_pos_dense(W.segCap, i, n);
-        shade(active, active ? q : 0);
+        if (!again) {   // the trip's first round
+            b.live = active;
+            b.dim = b.depth = 0;
+            b.index = 0;
+            if constexpr (CAMERA) camera_ray<SKY, kSmp, PASS>(W, pixTab, active, q, &b.ray, &b.dim, &b.index);   // level 0 only
+        }
+        again = shade(b, active ? q : 0);
     }
     __syncthreads();
     if (threadIdx.x == 0) { W.shadowSeg[wf_block()] = s_push[0]; W.next.segCount[wf_block()] = s_push[1]; }
