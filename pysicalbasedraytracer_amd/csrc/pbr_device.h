@@ -6,6 +6,7 @@
 #include "pbr_layout.h"
 #include "pbr_material.h"
 #include "pbr_math.h"
+#include "pbr_quad_order.h"
 #include "pbr_shading_frame.h"
 
 namespace pbr {
@@ -593,23 +594,51 @@ constexpr bool kPacket = PBR_PACKET != 0;
 #ifndef PBR_PACKET_EXTEND
 #define PBR_PACKET_EXTEND 1
 #endif
+// A wave-uniform lane mask as this lane's predicate: the mask is used as it stands (no per-lane
+// shift or compare).
+__device__ __forceinline__ bool lane_of(unsigned long long uniformMask) {
+    return __builtin_amdgcn_inverse_ballot_w64(uniformMask);
+}
+// slab_nf && tEnter < ray.tMax for the packet walk, as the mask of the lanes that pass: the same
+// float operations and the same comparisons, each comparison taken as the ballot of its lanes and
+// the conjunction formed on the masks, so the predicate never exists per lane.
+__device__ __forceinline__ unsigned long long slab_nf_lanes(f3 nr, f3 fr, const Ray& r, f3 inv) {
+    if constexpr (PBR_SLAB_BRANCHLESS) {
+        float tMin = (nr.x - r.o.x) * inv.x;
+        float tMax = (fr.x - r.o.x) * inv.x;
+        const float tyMin = (nr.y - r.o.y) * inv.y;
+        const float tyMax = (fr.y - r.o.y) * inv.y;
+        const float tzMin = (nr.z - r.o.z) * inv.z;
+        const float tzMax = (fr.z - r.o.z) * inv.z;
+        unsigned long long ok = __builtin_amdgcn_ballot_w64(!(tMin > tyMax)) & __builtin_amdgcn_ballot_w64(!(tyMin > tMax));
+        tMin = tyMin > tMin ? tyMin : tMin;
+        tMax = tyMax < tMax ? tyMax : tMax;
+        ok &= __builtin_amdgcn_ballot_w64(!(tMin > tzMax)) & __builtin_amdgcn_ballot_w64(!(tzMin > tMax));
+        tMin = tzMin > tMin ? tzMin : tMin;
+        tMax = tzMax < tMax ? tzMax : tMax;
+        return ok & __builtin_amdgcn_ballot_w64(tMax > 0) & __builtin_amdgcn_ballot_w64(tMin < r.tMax);
+    }
+    float t = 0.f;
+    return __builtin_amdgcn_ballot_w64(slab_nf(nr, fr, r, inv, &t) && t < r.tMax);
+}
 template <bool ANY>
 __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv, bool n0, bool n1, bool n2, bool alive,
                                 int u0, int u1, int u2) {
     const int wv = (int)(threadIdx.x >> 6);
     int* sref = s_pk_ref[wv];
     unsigned long long* smask = s_pk_mask[wv];
-    const unsigned long long lanebit = 1ull << __lane_id();
     int sp = 0;
     bool found = false;
     int cur = S.quadRootRef;
-    bool active = alive;
+    // the lanes active at the wave's current node, a wave-uniform mask like the ballots below
+    unsigned long long act = __builtin_amdgcn_ballot_w64(alive);
     // closest hit: the live lanes' common signs, wave-uniform, so the near/far plane selects of the
     // slab tests are scalar (any hit: each lane's own signs)
     if constexpr (!ANY) { n0 = u0 != 0; n1 = u1 != 0; n2 = u2 != 0; }
+    const int oct = u0 | (u1 << 1) | (u2 << 2);   // the sign octant, fixed for the whole walk
     while (true) {
         if (cur < 0) {   // leaf: the active lanes test its primitives in slot order
-            if (active) {
+            if (lane_of(act)) {
                 int slot = cur & 0x7fffffff;
                 while (true) {
                     const ScalarF4Ptr tv = scalar_f4(S.triVerts + 3 * (size_t)slot);
@@ -621,7 +650,7 @@ __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv,
                                          : tri_test(mk(v0.x, v0.y, v0.z), mk(v1.x, v1.y, v1.z), mk(v2.x, v2.y, v2.z), r, &t, &b0, &b1, &b2);
                     if (hit) {
                         found = true;
-                        if (ANY) { alive = false; active = false; break; }
+                        if (ANY) { alive = false; break; }
                         r.tMax = t;   // GeometricPrimitive::Intersect (Primitive.cpp:26)
                         h->slot = slot; h->b0 = b0; h->b1 = b1; h->b2 = b2;
                     }
@@ -648,57 +677,41 @@ __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv,
             }
             const float4 R = as_f4(w[6]);
             const int meta = __float_as_int(w[7].x);
-            float t[4] = {0.f, 0.f, 0.f, 0.f};
-            bool p[4];
-            if constexpr (PBR_SLAB_BRANCHLESS) {   // (the lane and valid masks applied after the tests)
-                p[0] = slab_nf(mk(NX.x, NY.x, NZ.x), mk(FX.x, FY.x, FZ.x), r, inv, &t[0]) & (t[0] < r.tMax);
-                p[1] = slab_nf(mk(NX.y, NY.y, NZ.y), mk(FX.y, FY.y, FZ.y), r, inv, &t[1]) & (t[1] < r.tMax);
-                p[2] = slab_nf(mk(NX.z, NY.z, NZ.z), mk(FX.z, FY.z, FZ.z), r, inv, &t[2]) & (t[2] < r.tMax);
-                p[3] = slab_nf(mk(NX.w, NY.w, NZ.w), mk(FX.w, FY.w, FZ.w), r, inv, &t[3]) & (t[3] < r.tMax);
-                p[0] = p[0] & active & (((meta >> 8) & 1) != 0);
-                p[1] = p[1] & active & (((meta >> 9) & 1) != 0);
-                p[2] = p[2] & active & (((meta >> 10) & 1) != 0);
-                p[3] = p[3] & active & (((meta >> 11) & 1) != 0);
-            } else {
-            p[0] = active && slab_nf(mk(NX.x, NY.x, NZ.x), mk(FX.x, FY.x, FZ.x), r, inv, &t[0]) && ((meta >> 8) & 1) && t[0] < r.tMax;
-            p[1] = active && slab_nf(mk(NX.y, NY.y, NZ.y), mk(FX.y, FY.y, FZ.y), r, inv, &t[1]) && ((meta >> 9) & 1) && t[1] < r.tMax;
-            p[2] = active && slab_nf(mk(NX.z, NY.z, NZ.z), mk(FX.z, FY.z, FZ.z), r, inv, &t[2]) && ((meta >> 10) & 1) && t[2] < r.tMax;
-            p[3] = active && slab_nf(mk(NX.w, NY.w, NZ.w), mk(FX.w, FY.w, FZ.w), r, inv, &t[3]) && ((meta >> 11) & 1) && t[3] < r.tMax;
-            }
-            const unsigned long long bm[4] = {__builtin_amdgcn_ballot_w64(p[0]), __builtin_amdgcn_ballot_w64(p[1]),
-                                              __builtin_amdgcn_ballot_w64(p[2]), __builtin_amdgcn_ballot_w64(p[3])};
-            // visit position → slot column (quad_slots' swaps; any hit: build order)
-            int col[4] = {0, 1, 2, 3};
+            // the lanes that pass each slot column: active here, the slot valid, its slab test passed
+            // with tEnter < tMax (any hit: a lane that found its hit is no longer alive)
+            const unsigned long long on = ANY ? act & __builtin_amdgcn_ballot_w64(alive) : act;
+            // all ones where meta's valid bit of the column is set (the bit, sign-extended)
+            auto valid = [meta](int c) { return (unsigned long long)(((long long)meta << (55 - c)) >> 63); };
+            unsigned long long m[4] = {
+                slab_nf_lanes(mk(NX.x, NY.x, NZ.x), mk(FX.x, FY.x, FZ.x), r, inv) & on & valid(0),
+                slab_nf_lanes(mk(NX.y, NY.y, NZ.y), mk(FX.y, FY.y, FZ.y), r, inv) & on & valid(1),
+                slab_nf_lanes(mk(NX.z, NY.z, NZ.z), mk(FX.z, FY.z, FZ.z), r, inv) & on & valid(2),
+                slab_nf_lanes(mk(NX.w, NY.w, NZ.w), mk(FX.w, FY.w, FZ.w), r, inv) & on & valid(3)};
+            // The four masks brought into visit order by three wave-uniform swaps (pbr_quad_order.h:
+            // quad_slots' swaps on the live lanes' common signs; any hit: build order), so `first` and
+            // the pushes test fixed positions and only a pushed or entered slot needs its column.
+            QuadSigns qs = {0, 0, 0};
             if constexpr (!ANY) {
-                // the live lanes' common direction signs (u0, u1, u2) on the three split axes
-                const int aN = meta & 3, aA = (meta >> 2) & 3, aB = (meta >> 4) & 3;
-                const int sN = aN == 0 ? u0 : (aN == 1 ? u1 : u2);
-                const int sA = aA == 0 ? u0 : (aA == 1 ? u1 : u2);
-                const int sB = aB == 0 ? u0 : (aB == 1 ? u1 : u2);
-                for (int pos = 0; pos < 4; ++pos) {
-                    const int hi = (pos >> 1) ^ sN;
-                    col[pos] = hi * 2 + ((pos & 1) ^ (hi == 0 ? sA : sB));
-                }
+                qs = quad_signs(meta, oct);
+                quad_visit_order(qs, m);
             }
-            int first = -1;
-            for (int pos = 0; pos < 4; ++pos)
-                if (first < 0 && bm[col[pos]] != 0ull) first = pos;
+            const int some = quad_nonzero(m);
             // unreachable: the upload refuses trees whose quad walk can need more (kQuadStackLimit)
-            if (first >= 0 && sp > kQuadStackLimit) {
+            if (some != 0 && sp > kQuadStackLimit) {
                 atomicOr(S.guard, kGuardStack);
                 break;
             }
-            if (first >= 0) {
-                for (int pos = 3; pos > first; --pos)
-                    if (bm[col[pos]] != 0ull) {
-                        sref[sp] = (cur << 2) | col[pos];   // every lane stores the same values
-                        smask[sp] = bm[col[pos]];
-                        ++sp;
-                    }
-                const int c = col[first];
-                active = c == 0 ? p[0] : (c == 1 ? p[1] : (c == 2 ? p[2] : p[3]));
-                cur = __float_as_int(c == 0 ? R.x : (c == 1 ? R.y : (c == 2 ? R.z : R.w)));
-                cur = __builtin_amdgcn_readfirstlane(cur);
+            if (some != 0) {
+                quad_push_later(qs, some, m, [&](int, int c, unsigned long long lanes) {
+                    sref[sp] = (cur << 2) | c;   // every lane stores the same values
+                    smask[sp] = lanes;
+                    ++sp;
+                });
+                const int c = quad_col(qs, quad_first(some));
+                // the lanes that passed the entered slot are the active ones there
+                act = (some & 1) ? m[0] : ((some & 2) ? m[1] : ((some & 4) ? m[2] : m[3]));
+                const int r0 = __float_as_int(R.x), r1 = __float_as_int(R.y), r2 = __float_as_int(R.z), r3 = __float_as_int(R.w);
+                cur = c == 0 ? r0 : (c == 1 ? r1 : (c == 2 ? r2 : r3));   // scalars: uniform
                 continue;
             }
         }
@@ -707,7 +720,9 @@ __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv,
         while (sp > 0) {
             --sp;
             const int e = __builtin_amdgcn_readfirstlane(sref[sp]);
-            const unsigned long long m = smask[sp];   // a uniform LDS address: the same value in every lane
+            const unsigned long long mv = smask[sp];   // a uniform LDS address: the same value in every lane
+            const unsigned long long m = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)mv) |
+                                         (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(mv >> 32)) << 32;
             const int parent = e >> 2, c = e & 3;
             const ScalarF4Ptr w = scalar_f4(S.quad + 8 * (size_t)parent);
             // the slot's one box: its six floats are scalars, column c of each row (PBR_NF_ROWS:
@@ -726,12 +741,10 @@ __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv,
                 fr = mk(n0 ? lo.x : hi.x, n1 ? lo.y : hi.y, n2 ? lo.z : hi.z);
             }
             const __attribute__((address_space(4))) float* rf = (const __attribute__((address_space(4))) float*)(size_t)(wf + 24);
-            float tt = 0.f;
-            bool a = (m & lanebit) != 0ull && (!ANY || alive);
-            if constexpr (PBR_SLAB_BRANCHLESS) a = a & slab_nf(nr, fr, r, inv, &tt) & (tt < r.tMax);
-            else a = a && slab_nf(nr, fr, r, inv, &tt) && tt < r.tMax;
-            if (__builtin_amdgcn_ballot_w64(a) != 0ull) {
-                active = a;
+            unsigned long long a = m & slab_nf_lanes(nr, fr, r, inv);
+            if (ANY) a &= __builtin_amdgcn_ballot_w64(alive);
+            if (a != 0ull) {
+                act = a;
                 cur = __builtin_amdgcn_readfirstlane(__float_as_int(rf[c]));
                 more = true;
                 break;

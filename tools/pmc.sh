@@ -17,7 +17,13 @@ run() {   # name counters...
   echo "pmc $name rc=$rc"
   return $rc
 }
-run sq ${SQ_COUNTERS:-SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD} &&
-run fetch FETCH_SIZE &&
-run write WRITE_SIZE &&
-run tcc TCC_HIT_sum TCC_MISS_sum
+# PASSES picks among sq, fetch, write, tcc (default all four); a pass that fails ends the script
+for pass in ${PASSES:-sq fetch write tcc}; do
+  case $pass in
+    sq) run sq ${SQ_COUNTERS:-SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD} ;;
+    fetch) run fetch FETCH_SIZE ;;
+    write) run write WRITE_SIZE ;;
+    tcc) run tcc TCC_HIT_sum TCC_MISS_sum ;;
+    *) echo "unknown pass $pass"; false ;;
+  esac || exit 1
+done
