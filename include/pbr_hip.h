@@ -24,6 +24,8 @@
  *   pbr_hip_render_aov    — (none): per-pixel albedo, coverage, normal and depth of the first surface the
  *                           same camera samples see, in the same resumable passes (feature buffers)
  *   pbr_hip_denoise       — (none): an edge-avoiding à-trous filter over those sums and feature buffers
+ *   pbr_hip_temporal      — (none): the previous frame's sums reprojected into this frame's (temporal
+ *                           accumulation; pbr_hip_camera_matrices gives it a camera's matrices)
  *   pbr_hip_destroy      — scene/integrator destructors
  *   pbr_hip_last_error    — (none; the reference fails silently)
  *   pbr_hip_sync          — (none; the reference's Render returns when the frame is done): waits
@@ -483,6 +485,65 @@ typedef struct pbr_denoise {
 } pbr_denoise;
 int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const int32_t* counts, const float* accum,
                     const float* aov, float* rgb_out, uint8_t* rgba_out, float* var_out, void* stream);
+
+/* ---- temporal accumulation (no reference counterpart) ----
+ * The temporal part of SVGF (Schied et al. 2017) as a merge of accumulators: the previous frame's sums are
+ * carried into this frame's, so that a moving camera at a few samples per frame does not start from nothing.
+ * Per pixel that hit something, the point its centre sees (the pinhole ray through the centre at the mean
+ * first-hit distance) is projected into the previous frame; the previous frame's per-sample means of L and L²
+ * are resampled there over the four surrounding pixels, each tap kept only where the previous frame saw a
+ * surface at the expected distance (tol_z, relative) with about the same mean normal (tol_n, squared
+ * difference) and holds finite sums; with demodulate the taps are resampled as colour / first-hit albedo and
+ * multiplied by this pixel's albedo.  The history enters as min(the taps' smallest count, max_history)
+ * samples: accum_out = accum_cur + history mean * that number, counts_out = count + that number, the format
+ * of accum and counts, so pbr_hip_denoise(counts = counts_out) and the variance estimate work on it
+ * unchanged.  A pixel without a hit, off the previous frame, behind the previous camera or without a valid
+ * tap keeps its own sums bit for bit.  Static scenes only: a moving object is not reprojected.  Every
+ * operation is float32 in the order DESIGN §4.8 states, nothing fused, no transcendental: the result is
+ * pinned bit for bit by a float32 restatement (tests/temporal_expected.py).
+ *
+ * pbr_hip_camera_matrices: the two matrices and the eye point such a call needs, from build_camera's own
+ * transforms of a descriptor (use_look_at and use_raster_to_camera honoured, lens_radius ignored), row
+ * major: raster_to_world = CameraToWorld · RasterToCamera, world_to_raster its inverse (the product of the
+ * stored inverses, no new inversion), eye = CameraToWorld applied to the origin.  Host only: no context, no
+ * GPU call.  PBR_E_INVALID: a NULL argument, width or height < 1.
+ *
+ * pbr_hip_temporal.  Buffers are device pointers over a width x height frame in raster order, row 0 first:
+ * accum_* 6 floats per pixel (the sums of pbr_hip_render_passes), aov_* the 8-float image of
+ * pbr_hip_render_aov, counts_prev (required) the samples behind each previous pixel, counts_cur the samples
+ * behind each current pixel (NULL: every pixel took `samples`; entries below 2^30 — the caller's contract).
+ * accum_out and counts_out are required; motion_out (2 floats per pixel: the pixel's raster position in the
+ * previous frame minus its position in this one, (0, 0) without a projection), rgb_out (accum_out's colour
+ * sum / counts_out, 0 where the count is 0) and rgba_out (its film transform) may each be NULL.  accum_out
+ * may be accum_cur and counts_out may be counts_cur (a pixel reads only its own current entry); an output
+ * pointer equal to counts_prev, accum_prev or aov_prev returns PBR_E_INVALID.  Asynchronous on `stream`
+ * (NULL: the context's) with the ordering of pbr_hip_denoise: calls on one stream follow each other, a call
+ * on another stream drains the context first, and pbr_hip_wait_frame(ctx, stream, 0) orders another stream
+ * after the call.  No scene is needed and nothing is allocated.
+ * PBR_E_INVALID: NULL ctx, p or a required buffer; width or height < 1; width * height >= 2^31; max_history
+ * outside 1..2^20; tol_z or tol_n negative or NaN; counts_cur == NULL with samples < 1; a NaN in either
+ * matrix or eye; the aliasing above.
+ *
+ * pbr_hip_temporal_host: the same per-pixel function compiled for the host, over host pointers, without the
+ * images; no context, no GPU call; the same refusals. */
+int pbr_hip_camera_matrices(const pbr_camera_desc* cam, float raster_to_world[16], float world_to_raster[16], float eye[3]);
+typedef struct pbr_temporal {
+    int width, height;          /* whole frame, raster order, row 0 first (as pbr_denoise) */
+    int max_history;            /* 1 .. 2^20: cap, in samples, of the history a pixel takes over */
+    int demodulate;             /* 1: history is resampled as colour / first-hit albedo */
+    float tol_z;                /* >= 0: relative distance tolerance of a tap; suggested 0.05 */
+    float tol_n;                /* >= 0: squared difference of the mean normals; suggested 0.1 */
+    float cur_raster_to_world[16];
+    float cur_eye[3];
+    float prev_world_to_raster[16];
+    float prev_eye[3];
+} pbr_temporal;
+int pbr_hip_temporal(pbr_hip_ctx* ctx, const pbr_temporal* p, int samples, const int32_t* counts_cur, const float* accum_cur,
+                     const float* aov_cur, const int32_t* counts_prev, const float* accum_prev, const float* aov_prev,
+                     float* accum_out, int32_t* counts_out, float* motion_out, float* rgb_out, uint8_t* rgba_out, void* stream);
+int pbr_hip_temporal_host(const pbr_temporal* p, int samples, const int32_t* counts_cur, const float* accum_cur,
+                          const float* aov_cur, const int32_t* counts_prev, const float* accum_prev, const float* aov_prev,
+                          float* accum_out, int32_t* counts_out, float* motion_out);
 
 /* ---- schedule (no reference counterpart) ----
  * How a frame is cut into launches on the device.  Every setting renders the same bits (the GPU

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi, scenes  # noqa: F401
 
-__all__ = ["AdaptiveRender", "HipRenderer", "ProgressiveRender", "capi", "scenes", "tile_grid", "tiles_for_rank"]
+__all__ = ["AdaptiveRender", "HipRenderer", "ProgressiveRender", "TemporalRender", "capi", "scenes", "tile_grid", "tiles_for_rank"]
 
 
 class PbrError(RuntimeError):
@@ -223,6 +223,93 @@ class HipRenderer:
         p.demodulate = 1 if demodulate else 0
         self._check(self.lib.pbr_hip_denoise(self.ctx, C.byref(p), int(samples), counts_ptr or None, accum_ptr, aov_ptr,
                                              rgb_ptr or None, rgba_ptr or None, var_ptr or None, stream), "denoise")
+
+    @staticmethod
+    def _check_temporal(who, width, height, samples, have_counts, max_history, tol_z, tol_n, cur, prev):
+        """The frame, parameters and cameras of a temporal merge, refused before any library call; returns
+        them as a capi.Temporal (demodulate left 0).  cur and prev: capi.camera_matrices() of the two cameras."""
+        width, height, samples, max_history = int(width), int(height), int(samples), int(max_history)
+        if width < 1 or height < 1:
+            raise ValueError(f"{who}: width and height must be >= 1")
+        if width * height >= 1 << 31:
+            raise ValueError(f"{who}: width * height must be below 2^31")
+        if not 1 <= max_history <= 1 << 20:
+            raise ValueError(f"{who}: max_history must be 1..2^20")
+        for name, v in (("tol_z", tol_z), ("tol_n", tol_n)):
+            if not float(v) >= 0.0:   # (a NaN fails the comparison)
+                raise ValueError(f"{who}: {name} must be >= 0")
+        if not have_counts and samples < 1:
+            raise ValueError(f"{who}: samples must be >= 1, or give per-pixel counts")
+        p = capi.Temporal(width, height, max_history, 0, float(tol_z), float(tol_n))
+        for name, cam in (("cur", cur), ("prev", prev)):
+            if cam is None or len(cam) != 3:
+                raise ValueError(f"{who}: {name} must be (raster_to_world, world_to_raster, eye) of capi.camera_matrices")
+        for field, name, a, n in (("cur_raster_to_world", "cur's raster_to_world", cur[0], 16), ("cur_eye", "cur's eye", cur[2], 3),
+                                  ("prev_world_to_raster", "prev's world_to_raster", prev[1], 16), ("prev_eye", "prev's eye", prev[2], 3)):
+            a = np.asarray(a, dtype=np.float32).reshape(-1)
+            if a.size != n:
+                raise ValueError(f"{who}: {name} must hold {n} floats")
+            if np.isnan(a).any():
+                raise ValueError(f"{who}: a NaN in {name}")
+            getattr(p, field)[:] = a.tolist()
+        return p
+
+    def temporal(self, width, height, samples, accum_cur_ptr, aov_cur_ptr, counts_prev_ptr, accum_prev_ptr, aov_prev_ptr,
+                 accum_out_ptr, counts_out_ptr, cur, prev, counts_cur_ptr=None, motion_ptr=None, rgb_ptr=None, rgba_ptr=None,
+                 max_history=32, demodulate=True, tol_z=0.05, tol_n=0.1, stream: int | None = None):
+        """Temporal accumulation (pbr_hip_temporal) over a width x height frame in raster order: the previous
+        frame's sums (accum_prev 6 float32 per pixel, counts_prev int32 per pixel, aov_prev its 8-float feature
+        image) are reprojected into this frame's (accum_cur, aov_cur; counts_cur or None: every pixel took
+        `samples`) and merged as at most max_history samples of history; accum_out / counts_out (which may be
+        the current buffers, never the previous ones) have the format of accum and counts, so
+        denoise(counts_ptr=counts_out) works on them.  cur and prev are capi.camera_matrices() of this frame's
+        and the previous frame's camera.  Optional outputs: motion_ptr 2 float32 per pixel, rgb_ptr 3 float32,
+        rgba_ptr its 8-bit film transform.  All device pointers.  Asynchronous, ordered as denoise;
+        wait_frame(stream, 0) orders another stream after it."""
+        p = self._check_temporal("temporal", width, height, samples, bool(counts_cur_ptr), max_history, tol_z, tol_n, cur, prev)
+        if not (accum_cur_ptr and aov_cur_ptr and counts_prev_ptr and accum_prev_ptr and aov_prev_ptr):
+            raise ValueError("temporal: accum_cur, aov_cur, counts_prev, accum_prev and aov_prev are required")
+        if not (accum_out_ptr and counts_out_ptr):
+            raise ValueError("temporal: accum_out and counts_out are required")
+        for out in (accum_out_ptr, counts_out_ptr, motion_ptr, rgb_ptr, rgba_ptr):
+            if out and out in (counts_prev_ptr, accum_prev_ptr, aov_prev_ptr):
+                raise ValueError("temporal: an output buffer is one of the previous frame's")
+        p.demodulate = 1 if demodulate else 0
+        self._check(self.lib.pbr_hip_temporal(self.ctx, C.byref(p), int(samples), counts_cur_ptr or None, accum_cur_ptr,
+                                              aov_cur_ptr, counts_prev_ptr, accum_prev_ptr, aov_prev_ptr, accum_out_ptr,
+                                              counts_out_ptr, motion_ptr or None, rgb_ptr or None, rgba_ptr or None, stream),
+                    "temporal")
+
+    def temporal_host(self, width, height, samples, accum_cur, aov_cur, counts_prev, accum_prev, aov_prev, cur, prev,
+                      counts_cur=None, max_history=32, demodulate=True, tol_z=0.05, tol_n=0.1):
+        """The same merge on the CPU over numpy arrays (pbr_hip_temporal_host: the device's per-pixel function
+        compiled for the host; no GPU call): returns (accum_out [n, 6] float32, counts_out [n] int32,
+        motion [n, 2] float32).  The inputs are left as they are."""
+        p = self._check_temporal("temporal_host", width, height, samples, counts_cur is not None, max_history, tol_z, tol_n,
+                                 cur, prev)
+        n = p.width * p.height
+        arrays = []
+        for name, a, dt, ch in (("accum_cur", accum_cur, np.float32, 6), ("aov_cur", aov_cur, np.float32, 8),
+                                ("counts_prev", counts_prev, np.int32, 1), ("accum_prev", accum_prev, np.float32, 6),
+                                ("aov_prev", aov_prev, np.float32, 8), ("counts_cur", counts_cur, np.int32, 1)):
+            if a is None:
+                if name != "counts_cur":
+                    raise ValueError(f"temporal_host: {name} is required")
+                arrays.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != n * ch:
+                raise ValueError(f"temporal_host: {name} holds {a.size} values, expected {n} x {ch}")
+            arrays.append(a)
+        a_cur, f_cur, c_prev, a_prev, f_prev, c_cur = arrays
+        p.demodulate = 1 if demodulate else 0
+        out, cnt, mot = np.empty((n, 6), np.float32), np.empty(n, np.int32), np.empty((n, 2), np.float32)
+        rc = self.lib.pbr_hip_temporal_host(C.byref(p), int(samples), c_cur.ctypes.data if c_cur is not None else None,
+                                            a_cur.ctypes.data, f_cur.ctypes.data, c_prev.ctypes.data, a_prev.ctypes.data,
+                                            f_prev.ctypes.data, out.ctypes.data, cnt.ctypes.data, mot.ctypes.data)
+        if rc != capi.PBR_OK:
+            raise PbrError(f"temporal_host failed ({rc})")
+        return out, cnt, mot
 
     @staticmethod
     def _check_rule(who, tolerance, floor):
@@ -732,6 +819,133 @@ class AdaptiveRender:
         self.samples_done = int(cnt.max()) if cnt.size else 0
         self.rounds = int(state.get("rounds", 0))
         self.active = None
+
+
+class TemporalRender:
+    """A camera path at a few samples per frame, each frame carrying the frames before it (temporal
+    accumulation, HipRenderer.temporal).
+
+    frame(camera) renders samples_per_frame samples of every pixel under `camera` — frame f draws the
+    sample numbers [s0, s0 + k), s0 = (f mod cycle) · k, so successive frames draw different samples —
+    with their feature buffers, reprojects the history it holds (the merged sums, counts and feature image
+    of the previous call, and that call's camera) into them, and keeps the result as the new history.
+    Owns the sums ([n, 6] float32), counts ([n] int32) and feature images ([n, 8] float32) as torch tensors
+    on the renderer's device, in raster order: the descriptor must have no tiles.  The scene is static;
+    after a new upload call reset()."""
+
+    def __init__(self, renderer: HipRenderer, rdesc, samples_per_frame, cycle=16, max_history=32, demodulate=True,
+                 tol_z=0.05, tol_n=0.1, device=None):
+        k, cycle = int(samples_per_frame), int(cycle)
+        if k < 1 or cycle < 1:
+            raise ValueError("TemporalRender: samples_per_frame and cycle must be >= 1")
+        budget = HipRenderer._pass_budget("TemporalRender", rdesc)
+        if k * cycle > budget:
+            raise ValueError(f"TemporalRender: {cycle} frames of {k} samples run past the budget of {budget} samples per "
+                             f"pixel (rdesc.spp)")
+        if rdesc.n_tiles:
+            raise ValueError("TemporalRender: a tiled descriptor (the merge works on a whole frame in raster order)")
+        w, h = rdesc.camera.width, rdesc.camera.height
+        ident = (np.eye(4, dtype=np.float32),) * 2 + (np.zeros(3, np.float32),)
+        HipRenderer._check_temporal("TemporalRender", w, h, k, False, max_history, tol_z, tol_n, ident, ident)
+        self.renderer, self.rdesc = renderer, rdesc
+        self.samples_per_frame, self.cycle = k, cycle
+        self.params = dict(max_history=int(max_history), demodulate=bool(demodulate), tol_z=float(tol_z), tol_n=float(tol_n))
+        self.width, self.height, self.n_pixels = w, h, w * h
+        self.frames_done = 0
+        self._device = device
+        self._sets = self._aov_sum = self._motion = self._rgb = self._rgba = self._stream = None
+        self._dn_rgb = self._dn_rgba = None
+        self._hist = None          # index of the set that holds the history (None: no history)
+        self._prev_cam = None      # capi.camera_matrices of the history's camera
+
+    def _buffers(self):
+        import torch
+        if self._sets is None:
+            dev = self._device if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            n = self.n_pixels
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            # two sets of (sums, counts, feature image): one holds the history, the other takes the frame
+            self._sets = [(z((n, 6), torch.float32), z((n,), torch.int32), z((n, capi.AOV_CHANNELS), torch.float32))
+                          for _ in range(2)]
+            self._aov_sum = z((n, capi.AOV_CHANNELS), torch.float32)
+            self._motion = z((n, 2), torch.float32)
+            self._rgb = z((n, 3), torch.float32)
+            self._rgba = z((n, 4), torch.uint8)
+            self._stream = torch.cuda.Stream(dev)   # (the library takes a real stream handle: ProgressiveRender)
+        return torch
+
+    def reset(self):
+        """Drops the history: the next frame is the plain samples_per_frame-sample frame."""
+        self._hist = None
+        self._prev_cam = None
+
+    def frame(self, camera):
+        """One frame under `camera` (a capi.CameraDesc of the descriptor's raster size): (rgb [n, 3] float32,
+        rgba [n, 4] uint8) device tensors of the merged image, reused by the next frame.  Asynchronous as
+        ProgressiveRender.step."""
+        if camera.width != self.width or camera.height != self.height:
+            raise ValueError(f"TemporalRender.frame: a {camera.width}x{camera.height} camera for a "
+                             f"{self.width}x{self.height} frame")
+        cam = capi.camera_matrices(camera, self.renderer.lib)
+        torch = self._buffers()
+        r, k, st = self.renderer, self.samples_per_frame, self._stream
+        d = type(self.rdesc).from_buffer_copy(self.rdesc)
+        d.camera = camera
+        s0 = (self.frames_done % self.cycle) * k
+        cur = 1 if self._hist == 0 else 0
+        acc, cnt, img = self._sets[cur]
+        hacc, hcnt, himg = self._sets[1 - cur]
+        current = torch.cuda.current_stream(acc.device)
+        st.wait_stream(current)   # (the tensors' initialisation, readers of the last image)
+        with torch.cuda.stream(st):
+            acc.zero_()
+            self._aov_sum.zero_()
+            if self._hist is None:
+                hcnt.zero_()   # (no history: a count of 0 drops every tap)
+        r.render_passes(d, s0, k, acc.data_ptr(), [None], [None], stream=st.cuda_stream)
+        r.render_aov(d, s0, k, self._aov_sum.data_ptr(), None, stream=st.cuda_stream)
+        with torch.cuda.stream(st):   # the feature image over these k samples (aov_out's formula)
+            f = self._aov_sum
+            img[:, 0:7] = f[:, 0:7] / torch.full_like(f[:, 0:7], float(k))   # (a tensor divisor: a true division)
+            hit = f[:, 3]
+            img[:, 7] = torch.where(hit > 0, f[:, 7] / hit, torch.zeros_like(hit))
+        r.temporal(self.width, self.height, k, acc.data_ptr(), img.data_ptr(), hcnt.data_ptr(), hacc.data_ptr(), himg.data_ptr(),
+                   acc.data_ptr(), cnt.data_ptr(), cam, self._prev_cam if self._prev_cam is not None else cam,
+                   motion_ptr=self._motion.data_ptr(), rgb_ptr=self._rgb.data_ptr(), rgba_ptr=self._rgba.data_ptr(),
+                   stream=st.cuda_stream, **self.params)
+        current.wait_stream(st)
+        self._hist, self._prev_cam = cur, cam
+        self.frames_done += 1
+        return self._rgb, self._rgba
+
+    def history(self) -> dict:
+        """The merged frame held as history, device tensors reused by later frames: sums [n, 6], counts [n],
+        features [n, 8] (this frame's own feature image) and motion [n, 2] of the last merge."""
+        if self._hist is None:
+            raise ValueError("TemporalRender.history: no frame yet (or reset)")
+        acc, cnt, img = self._sets[self._hist]
+        return {"accum": acc, "counts": cnt, "features": img, "motion": self._motion}
+
+    def denoise(self, iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0):
+        """The merged frame filtered (HipRenderer.denoise over the merged sums with counts = the merged
+        counts): (rgb [n, 3] float32, rgba [n, 4] uint8) device tensors of its own."""
+        if self._hist is None:
+            raise ValueError("TemporalRender.denoise: no frame yet (or reset)")
+        HipRenderer._check_denoise("TemporalRender.denoise", self.width, self.height, 0, True, iterations, sigma_l, sigma_n,
+                                   sigma_z)
+        torch = self._buffers()
+        acc, cnt, img = self._sets[self._hist]
+        if self._dn_rgb is None:
+            self._dn_rgb = torch.empty((self.n_pixels, 3), dtype=torch.float32, device=acc.device)
+            self._dn_rgba = torch.empty((self.n_pixels, 4), dtype=torch.uint8, device=acc.device)
+        current = torch.cuda.current_stream(acc.device)
+        self._stream.wait_stream(current)   # (readers of the last denoised image)
+        self.renderer.denoise(self.width, self.height, 0, acc.data_ptr(), img.data_ptr(), rgb_ptr=self._dn_rgb.data_ptr(),
+                              rgba_ptr=self._dn_rgba.data_ptr(), counts_ptr=cnt.data_ptr(), iterations=iterations,
+                              demodulate=demodulate, sigma_l=sigma_l, sigma_n=sigma_n, sigma_z=sigma_z,
+                              stream=self._stream.cuda_stream)
+        current.wait_stream(self._stream)
+        return self._dn_rgb, self._dn_rgba
 
 
 # Edge of the multi-GPU tiles.  Per-rank frame of an 8-GPU C2 job (slowest of 8 ranks, one GPU,

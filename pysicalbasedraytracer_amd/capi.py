@@ -303,6 +303,23 @@ class Denoise(C.Structure):
                 ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
 
 
+class Temporal(C.Structure):
+    """pbr_temporal: the frame, the merge's parameters and the two cameras' matrices (pbr_hip_temporal)."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("max_history", C.c_int), ("demodulate", C.c_int),
+                ("tol_z", C.c_float), ("tol_n", C.c_float),
+                ("cur_raster_to_world", F16), ("cur_eye", F3), ("prev_world_to_raster", F16), ("prev_eye", F3)]
+
+
+def camera_matrices(cam: "CameraDesc", lib=None):
+    """pbr_hip_camera_matrices: (raster_to_world [4, 4], world_to_raster [4, 4], eye [3]) float32 of a camera
+    descriptor, from the transforms a render of it uses (no context, no GPU call)."""
+    import numpy as np
+    r2w, w2r, eye = np.zeros((4, 4), np.float32), np.zeros((4, 4), np.float32), np.zeros(3, np.float32)
+    if (lib or load_library()).pbr_hip_camera_matrices(C.byref(cam), fptr(r2w), fptr(w2r), fptr(eye)) != PBR_OK:
+        raise ValueError("camera_matrices: width and height must be >= 1")
+    return r2w, w2r, eye
+
+
 # enum pbr_bsdf_variant (pbr_hip_bsdf): the lobe mask and template source of a production shading kernel
 (BSDF_VARIANT_ALL, BSDF_VARIANT_SIMPLE, BSDF_VARIANT_MATTE_MIRROR, BSDF_VARIANT_MICRO, BSDF_VARIANT_PASS_L,
  BSDF_VARIANT_PASS_R, BSDF_VARIANT_PASS_LR, BSDF_VARIANT_PASS_RT, BSDF_VARIANT_PASS_LRT, BSDF_VARIANT_MIRROR,
@@ -400,6 +417,10 @@ EXPORTS = {
                                    C.POINTER(C.c_int)]),
     "pbr_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(Denoise), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbr_hip_camera_matrices": (C.c_int, [C.POINTER(CameraDesc), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float)]),
+    "pbr_hip_temporal": (C.c_int, [C.c_void_p, C.POINTER(Temporal), C.c_int] + [C.c_void_p] * 12),
+    "pbr_hip_temporal_host": (C.c_int, [C.POINTER(Temporal), C.c_int] + [C.c_void_p] * 9),
     "pbr_hip_get_bvh": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int)]),
     "pbr_hip_sampler_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -444,7 +465,8 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_render_frames", "pbr_hip_wait_frame", "pbr_hip_render_passes", "pbr_hip_intersect_walk",
                    "pbr_hip_plan_chunks", "pbr_hip_last_chunks", "pbr_hip_adaptive_select", "pbr_hip_render_passes_list",
                    "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov", "pbr_hip_denoise", "pbr_hip_bsdf",
-                   "pbr_hip_bsdf_host", "pbr_hip_phase_hg", "pbr_hip_phase_hg_host", "pbr_hip_shading_host")
+                   "pbr_hip_bsdf_host", "pbr_hip_phase_hg", "pbr_hip_phase_hg_host", "pbr_hip_shading_host",
+                   "pbr_hip_camera_matrices", "pbr_hip_temporal", "pbr_hip_temporal_host")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

@@ -26,6 +26,7 @@
 #include "pbr_chunk_plan.h"
 #include "pbr_aov_plan.h"
 #include "pbr_probe_glue.h"
+#include "pbr_temporal.h"
 
 using namespace pbr;
 
@@ -694,6 +695,8 @@ __global__ __launch_bounds__(256, OCC) void k_render(KParams P) {
 #include "pbr_adaptive.h"
 #include "pbr_aov.h"
 #include "pbr_denoise.h"
+#define PBR_TEMPORAL_KERNEL
+#include "pbr_temporal.h"
 
 // ---------------------------------------------------------------- introspection kernels
 __global__ void k_sampler_values(DeviceSampler smp, HaltonParams hp, int n, const int32_t* q, float* out) {
@@ -2970,6 +2973,46 @@ int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const i
     return PBR_OK;
 }
 
+// ---- temporal accumulation (pbr_temporal.h)
+int pbr_hip_temporal(pbr_hip_ctx* ctx, const pbr_temporal* p, int samples, const int32_t* counts_cur, const float* accum_cur,
+                     const float* aov_cur, const int32_t* counts_prev, const float* accum_prev, const float* aov_prev,
+                     float* accum_out, int32_t* counts_out, float* motion_out, float* rgb_out, uint8_t* rgba_out, void* stream) {
+    if (!ctx) return PBR_E_INVALID;
+    if (const char* what = tp_params_error(p, samples, counts_cur)) return set_err(ctx, PBR_E_INVALID, what);
+    if (!accum_cur || !aov_cur || !counts_prev || !accum_prev || !aov_prev)
+        return set_err(ctx, PBR_E_INVALID, "temporal: accum_cur, aov_cur, counts_prev, accum_prev and aov_prev are required");
+    if (!accum_out || !counts_out) return set_err(ctx, PBR_E_INVALID, "temporal: accum_out and counts_out are required");
+    for (const void* out : {(const void*)accum_out, (const void*)counts_out, (const void*)motion_out, (const void*)rgb_out,
+                            (const void*)rgba_out})
+        if (tp_output_is_history(out, counts_prev, accum_prev, aov_prev))
+            return set_err(ctx, PBR_E_INVALID, "temporal: an output buffer is one of the previous frame's");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    // the ordering of a denoise call: a call on another stream drains the context first
+    if (ctx->lastStream != s) {
+        if (int rc = drain(ctx)) return rc;
+    }
+    const int W = p->width, H = p->height;
+    const long long npx = (long long)W * H;
+    const int nbx = (W + kDnTW - 1) / kDnTW, nby = (H + kDnTH - 1) / kDnTH;
+    const dim3 grid((unsigned)((long long)nbx * nby)), blk(kDnBlock);   // (below 2^31 tiles: npx is)
+    ctx->batchFrames = 0;   // (set when the call is queued)
+    begin_lanes(ctx, s);
+    PROF_LAUNCH(KP_TP_ACCUMULATE, s,
+        hipLaunchKernelGGL(k_tp_accumulate, grid, blk, 0, s, *p, nbx, samples, counts_cur, accum_cur, aov_cur, counts_prev,
+                           accum_prev, aov_prev, accum_out, counts_out, motion_out, rgb_out, (uint32_t*)rgba_out));
+    HIP_TRY(hipGetLastError());
+    prof_host(ctx, KP_TP_ACCUMULATE, 0, (unsigned long long)npx);
+    if (counts_cur) prof_host(ctx, KP_TP_ACCUMULATE, 1, (unsigned long long)npx);
+    if (motion_out) prof_host(ctx, KP_TP_ACCUMULATE, 2, (unsigned long long)npx);
+    if (rgb_out) prof_host(ctx, KP_TP_ACCUMULATE, 3, (unsigned long long)npx);
+    if (rgba_out) prof_host(ctx, KP_TP_ACCUMULATE, 4, (unsigned long long)npx);
+    if (int rc = one_pass_done(ctx, s)) return rc;
+    ctx->inFlight = true;
+    ctx->lastStream = s;
+    return PBR_OK;
+}
+
 int pbr_hip_wait_frame(pbr_hip_ctx* ctx, void* stream, int f) {
     if (!ctx) return PBR_E_INVALID;
     if (f < 0 || f >= ctx->batchFrames) return set_err(ctx, PBR_E_INVALID, "wait_frame: no such frame in the last batch");
@@ -3073,7 +3116,7 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         "k_wfp_camera_extend", "k_wfp_shade", "k_wfp_shadow", "k_wfp_probe", "k_wfp_resolve", "k_wfp_finish",
         "k_wfv_shade", "k_wfv_tr", "k_wfv_resolve", "k_render", "k_wf_shade_l0", "k_aov", "k_aov_tex",
         "k_dn_prepare", "k_dn_atrous_l0", "k_dn_atrous_l1", "k_dn_atrous_l2", "k_dn_atrous_l3", "k_dn_atrous_l4",
-        "k_dn_atrous_l5", "k_dn_atrous_l6", "k_dn_atrous_l7", "k_dn_finish"};
+        "k_dn_atrous_l5", "k_dn_atrous_l6", "k_dn_atrous_l7", "k_dn_finish", "k_tp_accumulate"};
     unsigned long long c[KP_COUNT][kProfFields];
     std::memset(c, 0, sizeof(c));
     if (ctx->profOn) HIP_TRY(hipMemcpy(c, ctx->dProf.p, sizeof(c), hipMemcpyDeviceToHost));
@@ -3122,6 +3165,10 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         // read, f[1] rgb, f[2] rgba and f[3] variance pixels written
         case KP_DN_PREPARE: return 104 * f[0] + 4 * f[1];
         case KP_DN_FINISH: return 32 * f[0] + 12 * f[1] + 4 * f[2] + 4 * f[3];
+        // the temporal merge, f[0] pixels: this frame's sums 24 + features 32 read, the previous frame's sums,
+        // features and counts (60, each entry once: the four taps of neighbouring pixels overlap) read, sums
+        // 24 + counts 4 written; f[1] pixels read a count of their own, f[2] write the motion, f[3] rgb, f[4] rgba
+        case KP_TP_ACCUMULATE: return 144 * f[0] + 4 * f[1] + 8 * f[2] + 12 * f[3] + 4 * f[4];
         default:
             if (k >= KP_DN_LEVEL0 && k < KP_DN_LEVEL0 + 8) return 48 * f[0];
             return 16 * f[1];                                                  // megakernel: the film output

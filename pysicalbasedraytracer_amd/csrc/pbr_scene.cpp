@@ -11,6 +11,7 @@
 #include "pbr_shading_frame.h"
 #include "pbr_material.h"
 #include "pbr_sobol_jk.h"
+#include "pbr_temporal.h"
 #include "pbr_xform.h"
 
 #include <algorithm>
@@ -740,8 +741,9 @@ void light_distribution(const HostScene& s, int strategy, std::vector<float>* cd
     distribution1d(*func, cdf, funcInt);
 }
 
-void build_camera(const pbr_camera_desc* c, DeviceCamera* out) {
-    if (c->width <= 0 || c->height <= 0) fail("bad raster size");
+// CameraToWorld and RasterToCamera of a descriptor, each with its inverse (build_camera,
+// pbr_hip_camera_matrices).
+static void camera_xforms(const pbr_camera_desc* c, Xf* camToWorldOut, Xf* rasterToCameraOut) {
     Xf camToWorld;
     if (c->use_look_at) {
         camToWorld = inverse(look_at(mk(c->eye[0], c->eye[1], c->eye[2]), mk(c->look[0], c->look[1], c->look[2]),
@@ -761,6 +763,14 @@ void build_camera(const pbr_camera_desc* c, DeviceCamera* out) {
     Xf rasterToCamera = compose(inverse(camToScreen), inverse(screenToRaster));
     // a camera's own RasterToCamera (any fov / screen window): used as given
     if (c->use_raster_to_camera) rasterToCamera = Xf{from_rows(c->raster_to_camera.m), from_rows(c->raster_to_camera.m_inv)};
+    *camToWorldOut = camToWorld;
+    *rasterToCameraOut = rasterToCamera;
+}
+
+void build_camera(const pbr_camera_desc* c, DeviceCamera* out) {
+    if (c->width <= 0 || c->height <= 0) fail("bad raster size");
+    Xf camToWorld, rasterToCamera;
+    camera_xforms(c, &camToWorld, &rasterToCamera);
     std::memcpy(out->rasterToCamera, &rasterToCamera.m.a[0][0], 64);
     std::memcpy(out->cameraToWorld, &camToWorld.m.a[0][0], 64);
     out->lensRadius = c->lens_radius;
@@ -902,7 +912,49 @@ void sobol_pixel_tables(const uint32_t* mats, int m, std::vector<uint32_t>* out)
     for (int k = 0; k < kSobolMatrixSize - n; ++k) (*out)[n + k] = col(n + k);
 }
 
+// The matrices a temporal merge takes (pbr_hip_camera_matrices), from build_camera's own transforms.
+void camera_matrices(const pbr_camera_desc* c, float* rasterToWorld, float* worldToRaster, float* eye) {
+    Xf camToWorld, rasterToCamera;
+    camera_xforms(c, &camToWorld, &rasterToCamera);
+    const Xf r2w = compose(camToWorld, rasterToCamera);
+    std::memcpy(rasterToWorld, &r2w.m.a[0][0], 64);
+    std::memcpy(worldToRaster, &r2w.mi.a[0][0], 64);
+    // Transform::operator()(Point3f) on the origin
+    const Mat& m = camToWorld.m;
+    const float w = m.a[3][3];
+    for (int i = 0; i < 3; ++i) eye[i] = w == 1.f ? m.a[i][3] : m.a[i][3] / w;
+}
+
 }  // namespace pbr
+
+extern "C" int pbr_hip_camera_matrices(const pbr_camera_desc* cam, float raster_to_world[16], float world_to_raster[16],
+                                       float eye[3]) {
+    if (!cam || !raster_to_world || !world_to_raster || !eye) return PBR_E_INVALID;
+    if (cam->width < 1 || cam->height < 1) return PBR_E_INVALID;
+    pbr::camera_matrices(cam, raster_to_world, world_to_raster, eye);
+    return PBR_OK;
+}
+
+// pbr_hip_temporal_host: tp_pixel (pbr_temporal.h) over host buffers, on the CPU
+extern "C" int pbr_hip_temporal_host(const pbr_temporal* p, int samples, const int32_t* counts_cur, const float* accum_cur,
+                                     const float* aov_cur, const int32_t* counts_prev, const float* accum_prev,
+                                     const float* aov_prev, float* accum_out, int32_t* counts_out, float* motion_out) {
+    if (pbr::tp_params_error(p, samples, counts_cur)) return PBR_E_INVALID;
+    if (!accum_cur || !aov_cur || !counts_prev || !accum_prev || !aov_prev || !accum_out || !counts_out) return PBR_E_INVALID;
+    if (pbr::tp_output_is_history(accum_out, counts_prev, accum_prev, aov_prev) ||
+        pbr::tp_output_is_history(counts_out, counts_prev, accum_prev, aov_prev) ||
+        pbr::tp_output_is_history(motion_out, counts_prev, accum_prev, aov_prev))
+        return PBR_E_INVALID;
+    for (int y = 0; y < p->height; ++y)
+        for (int x = 0; x < p->width; ++x) {
+            const pbr::TpPixel o = pbr::tp_pixel(*p, x, y, samples, counts_cur, accum_cur, aov_cur, counts_prev, accum_prev, aov_prev);
+            const size_t q = (size_t)y * p->width + x;
+            for (int c = 0; c < 6; ++c) accum_out[6 * q + c] = o.s[c];
+            counts_out[q] = o.count;
+            if (motion_out) { motion_out[2 * q] = o.mx; motion_out[2 * q + 1] = o.my; }
+        }
+    return PBR_OK;
+}
 
 // pbr_hip_shading_host: shading_frame (pbr_shading_frame.h) on caller-given triangles, on the CPU
 extern "C" int pbr_hip_shading_host(int n, const pbr_shading_query* queries, float* out) {

@@ -44,6 +44,7 @@ enum ProfKind {
     KP_AOV, KP_AOV_TEX,   // feature passes (pbr_aov.h): the untextured and the textured instantiations
     // the denoiser (pbr_denoise.h): prepare, one family per wavelet level (8 of them), finish
     KP_DN_PREPARE, KP_DN_LEVEL0, KP_DN_FINISH = KP_DN_LEVEL0 + 8,
+    KP_TP_ACCUMULATE,   // the temporal merge (pbr_temporal.h)
     KP_COUNT
 };
 constexpr int kProfFields = 8;

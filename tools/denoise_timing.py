@@ -86,35 +86,10 @@ def stat(t):
             "spread": (max(t) - min(t)) / statistics.median(t), "ms": t}
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--parent", help="libpbr_hip.so built from the parent commit")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--steps", type=int, default=2)
-    ap.add_argument("--configs", nargs="*", default=["C2", "C3"], choices=["C2", "C3", "C5"])
-    ap.add_argument("--levels", type=int, default=5)
-    ap.add_argument("--json")
-    ap.add_argument("--md", help="write the result lines as a markdown document")
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("denoise_timing: no GPU (times are measured on the device or not at all)")
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
-    st = stream.cuda_stream
-    this = capi.load_library()
-    parent = capi.load_library(os.path.abspath(a.parent)) if a.parent else None
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    say(f"this build: {this.pbr_hip_build_info().decode()}")
-    if parent:
-        say(f"parent:     {parent.pbr_hip_build_info().decode()}")
-    out = {"rounds": a.rounds, "steps": a.steps, "levels": a.levels, "configs": {}, "denoise": {}}
+def plain_frames(a, this, parent, dev, st, say, out):
+    """(a): the plain frames of a.configs, this build against the parent's; fills out["configs"] and returns
+    whether every plain frame stayed within the bound.  (Shared with tools/temporal_timing.py.)"""
     ok = True
-    # ---- (a) plain frames against the parent's
     for cfg in a.configs:
         scene, rd = scenes.CONFIGS[cfg](1920, 1080)
         npx = 1920 * 1080
@@ -162,6 +137,38 @@ def main():
             res["plain_vs_parent"] = {"slower": slower, "bound": bound, "pass": slower <= bound}
         out["configs"][cfg] = res
         del rgb, rgba
+    return ok
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--parent", help="libpbr_hip.so built from the parent commit")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--configs", nargs="*", default=["C2", "C3"], choices=["C2", "C3", "C5"])
+    ap.add_argument("--levels", type=int, default=5)
+    ap.add_argument("--json")
+    ap.add_argument("--md", help="write the result lines as a markdown document")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("denoise_timing: no GPU (times are measured on the device or not at all)")
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    st = stream.cuda_stream
+    this = capi.load_library()
+    parent = capi.load_library(os.path.abspath(a.parent)) if a.parent else None
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"this build: {this.pbr_hip_build_info().decode()}")
+    if parent:
+        say(f"parent:     {parent.pbr_hip_build_info().decode()}")
+    out = {"rounds": a.rounds, "steps": a.steps, "levels": a.levels, "configs": {}, "denoise": {}}
+    # ---- (a) plain frames against the parent's
+    ok = plain_frames(a, this, parent, dev, st, say, out)
     # ---- (b) the denoise call
     r = renderer(this)
     frames = {}
