@@ -7,6 +7,8 @@
 #include "pbr_material.h"
 #include "pbr_math.h"
 #include "pbr_quad_order.h"
+#include "pbr_slab.h"
+#include <type_traits>
 #include "pbr_shading_frame.h"
 
 namespace pbr {
@@ -259,7 +261,28 @@ __device__ __forceinline__ bool prim_hit(const DeviceScene& S, int slot, const R
 #ifndef PBR_SLAB_BRANCHLESS
 #define PBR_SLAB_BRANCHLESS 1
 #endif
+// PBR_SLAB_FOLD: the packet walk tests foldable rays (pbr_slab.h: finite non-zero inv, finite origin,
+// in a scene whose boxes are finite and ordered) with slab_fold, the same decisions and the same
+// tEnter in 17 VALU and 2 mask conjunctions per slot instead of 26 and 5; every other ray keeps the
+// sequence below.  0 compiles the code before it.  PBR_SLAB_FOLD_LANE: the same for the per-lane quad
+// walks (traverse_quad and the lane-refill walks), decided per wave.
+#ifndef PBR_SLAB_FOLD
+#define PBR_SLAB_FOLD 1
+#endif
+#ifndef PBR_SLAB_FOLD_LANE
+#define PBR_SLAB_FOLD_LANE 0
+#endif
+// This lane's ray may not take the folded form (wave-uniform part: the scene's boxes).
+__device__ __forceinline__ bool slab_needs_exact(const DeviceScene& S, const Ray& r, f3 inv) {
+    return S.slabExact != 0 || !slab_ray_foldable(r.o.x, r.o.y, r.o.z, inv.x, inv.y, inv.z);
+}
+template <bool FOLD = false>
 __device__ __forceinline__ bool slab_nf(f3 nr, f3 fr, const Ray& r, f3 inv, float* tEnter) {
+    if constexpr (FOLD) {
+        const Slab s = slab_fold(nr.x, nr.y, nr.z, fr.x, fr.y, fr.z, r.o.x, r.o.y, r.o.z, inv.x, inv.y, inv.z, r.tMax);
+        *tEnter = s.tMin;
+        return s.order & s.ahead;
+    }
     if constexpr (PBR_SLAB_BRANCHLESS) {
         float tMin = (nr.x - r.o.x) * inv.x;
         float tMax = (fr.x - r.o.x) * inv.x;
@@ -291,8 +314,9 @@ __device__ __forceinline__ bool slab_nf(f3 nr, f3 fr, const Ray& r, f3 inv, floa
     *tEnter = tMin;
     return tMax > 0;
 }
+template <bool FOLD = false>
 __device__ __forceinline__ bool node_slab(f3 lo, f3 hi, const Ray& r, f3 inv, bool n0, bool n1, bool n2, float* tEnter) {
-    return slab_nf(mk(n0 ? hi.x : lo.x, n1 ? hi.y : lo.y, n2 ? hi.z : lo.z),
+    return slab_nf<FOLD>(mk(n0 ? hi.x : lo.x, n1 ? hi.y : lo.y, n2 ? hi.z : lo.z),
                    mk(n0 ? lo.x : hi.x, n1 ? lo.y : hi.y, n2 ? lo.z : hi.z), r, inv, tEnter);
 }
 
@@ -376,7 +400,7 @@ struct QuadSlots {   // one quad node's four slots in visit order
 };
 // A quad node's four slots from its fetched 128 B (LX..HZ: SoA boxes, R: child refs, meta: axes,
 // valid mask).
-template <bool ANY>
+template <bool ANY, bool FOLD = false>
 __device__ __forceinline__ void quad_slots_nf(float4 NX, float4 NY, float4 NZ, float4 FX, float4 FY, float4 FZ, float4 R,
                                               int meta, const Ray& r, f3 inv, bool n0, bool n1, bool n2, QuadSlots* q);
 // PBR_NF_ROWS: the near and far planes of a quad node are fetched as rows picked by the direction
@@ -389,10 +413,11 @@ __device__ __forceinline__ void quad_slots_nf(float4 NX, float4 NY, float4 NZ, f
 #ifndef PBR_NF_ROWS
 #define PBR_NF_ROWS 1
 #endif
-template <bool ANY>
+template <bool ANY, bool FOLD = false>
 __device__ __forceinline__ void quad_slots_lohi(float4 LX, float4 LY, float4 LZ, float4 HX, float4 HY, float4 HZ, float4 R,
                                                 int meta, const Ray& r, f3 inv, bool n0, bool n1, bool n2, QuadSlots* q);
-template <bool ANY, bool NF = false>
+// FOLD (PBR_SLAB_FOLD_LANE): the caller has found every active lane's ray foldable (slab_needs_exact)
+template <bool ANY, bool NF = false, bool FOLD = false>
 __device__ __forceinline__ void quad_slots(const DeviceScene& S, int cur, const Ray& r, f3 inv, bool n0, bool n1, bool n2,
                                            QuadSlots* q) {
     if constexpr (!NF || !PBR_NF_ROWS) {   // lo and hi fetched, each plane picked per slot (node_slab)
@@ -409,7 +434,7 @@ __device__ __forceinline__ void quad_slots(const DeviceScene& S, int cur, const 
             LX = w[0]; LY = w[1]; LZ = w[2]; HX = w[3]; HY = w[4]; HZ = w[5]; R = w[6];
             meta = __float_as_int(w[7].x);
         }
-        quad_slots_lohi<ANY>(LX, LY, LZ, HX, HY, HZ, R, meta, r, inv, n0, n1, n2, q);
+        quad_slots_lohi<ANY, FOLD>(LX, LY, LZ, HX, HY, HZ, R, meta, r, inv, n0, n1, n2, q);
         return;
     }
     float4 NX, NY, NZ, FX, FY, FZ, R;
@@ -435,31 +460,31 @@ __device__ __forceinline__ void quad_slots(const DeviceScene& S, int cur, const 
         R = w[6];
         meta = __float_as_int(w[7].x);
     }
-    quad_slots_nf<ANY>(NX, NY, NZ, FX, FY, FZ, R, meta, r, inv, n0, n1, n2, q);
+    quad_slots_nf<ANY, FOLD>(NX, NY, NZ, FX, FY, FZ, R, meta, r, inv, n0, n1, n2, q);
 }
 template <bool ANY>
 __device__ __forceinline__ void quad_order(bool k0, bool k1, bool k2, bool k3, float t0, float t1, float t2, float t3,
                                            float4 R, int meta, bool n0, bool n1, bool n2, QuadSlots* q);
-template <bool ANY>
+template <bool ANY, bool FOLD>
 __device__ __forceinline__ void quad_slots_lohi(float4 LX, float4 LY, float4 LZ, float4 HX, float4 HY, float4 HZ, float4 R,
                                                 int meta, const Ray& r, f3 inv, bool n0, bool n1, bool n2, QuadSlots* q) {
     float t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    bool k0 = node_slab(mk(LX.x, LY.x, LZ.x), mk(HX.x, HY.x, HZ.x), r, inv, n0, n1, n2, &t0) & ((meta >> 8) & 1);
-    bool k1 = node_slab(mk(LX.y, LY.y, LZ.y), mk(HX.y, HY.y, HZ.y), r, inv, n0, n1, n2, &t1) & ((meta >> 9) & 1);
-    bool k2 = node_slab(mk(LX.z, LY.z, LZ.z), mk(HX.z, HY.z, HZ.z), r, inv, n0, n1, n2, &t2) & ((meta >> 10) & 1);
-    bool k3 = node_slab(mk(LX.w, LY.w, LZ.w), mk(HX.w, HY.w, HZ.w), r, inv, n0, n1, n2, &t3) & ((meta >> 11) & 1);
+    bool k0 = node_slab<FOLD>(mk(LX.x, LY.x, LZ.x), mk(HX.x, HY.x, HZ.x), r, inv, n0, n1, n2, &t0) & ((meta >> 8) & 1);
+    bool k1 = node_slab<FOLD>(mk(LX.y, LY.y, LZ.y), mk(HX.y, HY.y, HZ.y), r, inv, n0, n1, n2, &t1) & ((meta >> 9) & 1);
+    bool k2 = node_slab<FOLD>(mk(LX.z, LY.z, LZ.z), mk(HX.z, HY.z, HZ.z), r, inv, n0, n1, n2, &t2) & ((meta >> 10) & 1);
+    bool k3 = node_slab<FOLD>(mk(LX.w, LY.w, LZ.w), mk(HX.w, HY.w, HZ.w), r, inv, n0, n1, n2, &t3) & ((meta >> 11) & 1);
     quad_order<ANY>(k0, k1, k2, k3, t0, t1, t2, t3, R, meta, n0, n1, n2, q);
 }
-template <bool ANY>
+template <bool ANY, bool FOLD>
 __device__ __forceinline__ void quad_slots_nf(float4 NX, float4 NY, float4 NZ, float4 FX, float4 FY, float4 FZ, float4 R,
                                               int meta, const Ray& r, f3 inv, bool n0, bool n1, bool n2, QuadSlots* q) {
     // (The two-slot pairs written as packed fp32 — v_pk_add/v_pk_mul — measured slower: 8-9 more
     // VGPRs, C4-material extend 119.5 → 129.0 ms; profiles/r5_slp_ab.log.)
     float t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    bool k0 = slab_nf(mk(NX.x, NY.x, NZ.x), mk(FX.x, FY.x, FZ.x), r, inv, &t0) & ((meta >> 8) & 1);
-    bool k1 = slab_nf(mk(NX.y, NY.y, NZ.y), mk(FX.y, FY.y, FZ.y), r, inv, &t1) & ((meta >> 9) & 1);
-    bool k2 = slab_nf(mk(NX.z, NY.z, NZ.z), mk(FX.z, FY.z, FZ.z), r, inv, &t2) & ((meta >> 10) & 1);
-    bool k3 = slab_nf(mk(NX.w, NY.w, NZ.w), mk(FX.w, FY.w, FZ.w), r, inv, &t3) & ((meta >> 11) & 1);
+    bool k0 = slab_nf<FOLD>(mk(NX.x, NY.x, NZ.x), mk(FX.x, FY.x, FZ.x), r, inv, &t0) & ((meta >> 8) & 1);
+    bool k1 = slab_nf<FOLD>(mk(NX.y, NY.y, NZ.y), mk(FX.y, FY.y, FZ.y), r, inv, &t1) & ((meta >> 9) & 1);
+    bool k2 = slab_nf<FOLD>(mk(NX.z, NY.z, NZ.z), mk(FX.z, FY.z, FZ.z), r, inv, &t2) & ((meta >> 10) & 1);
+    bool k3 = slab_nf<FOLD>(mk(NX.w, NY.w, NZ.w), mk(FX.w, FY.w, FZ.w), r, inv, &t3) & ((meta >> 11) & 1);
     quad_order<ANY>(k0, k1, k2, k3, t0, t1, t2, t3, R, meta, n0, n1, n2, q);
 }
 // the four slots in visit order (closest hit) or build order (any hit)
@@ -485,7 +510,7 @@ __device__ __forceinline__ void quad_order(bool k0, bool k1, bool k2, bool k3, f
     q->k[0] = k0; q->k[1] = k1; q->k[2] = k2; q->k[3] = k3;
 }
 
-template <bool ANY, int SHORT>
+template <bool ANY, int SHORT, bool FOLD = false>
 __device__ bool traverse_quad(const DeviceScene& S, Ray& r, HitRec* h, f3 inv, bool n0, bool n1, bool n2) {
     constexpr int PRIV = kTraversalStack - SHORT;
     int stackRef[PRIV];
@@ -535,7 +560,7 @@ __device__ bool traverse_quad(const DeviceScene& S, Ray& r, HitRec* h, f3 inv, b
             }
         } else {
             QuadSlots q;
-            quad_slots<ANY>(S, cur, r, inv, n0, n1, n2, &q);
+            quad_slots<ANY, false, FOLD>(S, cur, r, inv, n0, n1, n2, &q);
             const float tM = r.tMax;
             const bool p0 = q.k[0] && q.t[0] < tM, p1 = q.k[1] && q.t[1] < tM, p2 = q.k[2] && q.t[2] < tM,
                        p3 = q.k[3] && q.t[3] < tM;
@@ -602,7 +627,12 @@ __device__ __forceinline__ bool lane_of(unsigned long long uniformMask) {
 // slab_nf && tEnter < ray.tMax for the packet walk, as the mask of the lanes that pass: the same
 // float operations and the same comparisons, each comparison taken as the ballot of its lanes and
 // the conjunction formed on the masks, so the predicate never exists per lane.
+template <bool FOLD>
 __device__ __forceinline__ unsigned long long slab_nf_lanes(f3 nr, f3 fr, const Ray& r, f3 inv) {
+    if constexpr (FOLD) {
+        const Slab s = slab_fold(nr.x, nr.y, nr.z, fr.x, fr.y, fr.z, r.o.x, r.o.y, r.o.z, inv.x, inv.y, inv.z, r.tMax);
+        return __builtin_amdgcn_ballot_w64(s.order) & __builtin_amdgcn_ballot_w64(s.ahead) & __builtin_amdgcn_ballot_w64(s.within);
+    }
     if constexpr (PBR_SLAB_BRANCHLESS) {
         float tMin = (nr.x - r.o.x) * inv.x;
         float tMax = (fr.x - r.o.x) * inv.x;
@@ -621,9 +651,13 @@ __device__ __forceinline__ unsigned long long slab_nf_lanes(f3 nr, f3 fr, const 
     float t = 0.f;
     return __builtin_amdgcn_ballot_w64(slab_nf(nr, fr, r, inv, &t) && t < r.tMax);
 }
+// fold (wave-uniform): every lane active in this walk holds a foldable ray (traverse_wave) — the node
+// step and the pop step test with slab_fold.  A run-time flag, not a second instantiation: with both
+// walks in one kernel the scalar registers they keep live spilled (level 0: 64 B of scratch for 32,
+// C2 11.79 ms against 11.68; DESIGN.md §7 "Slab fold results").
 template <bool ANY>
 __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv, bool n0, bool n1, bool n2, bool alive,
-                                int u0, int u1, int u2) {
+                                int u0, int u1, int u2, bool fold = false) {
     const int wv = (int)(threadIdx.x >> 6);
     int* sref = s_pk_ref[wv];
     unsigned long long* smask = s_pk_mask[wv];
@@ -682,11 +716,35 @@ __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv,
             const unsigned long long on = ANY ? act & __builtin_amdgcn_ballot_w64(alive) : act;
             // all ones where meta's valid bit of the column is set (the bit, sign-extended)
             auto valid = [meta](int c) { return (unsigned long long)(((long long)meta << (55 - c)) >> 63); };
-            unsigned long long m[4] = {
-                slab_nf_lanes(mk(NX.x, NY.x, NZ.x), mk(FX.x, FY.x, FZ.x), r, inv) & on & valid(0),
-                slab_nf_lanes(mk(NX.y, NY.y, NZ.y), mk(FX.y, FY.y, FZ.y), r, inv) & on & valid(1),
-                slab_nf_lanes(mk(NX.z, NY.z, NZ.z), mk(FX.z, FY.z, FZ.z), r, inv) & on & valid(2),
-                slab_nf_lanes(mk(NX.w, NY.w, NZ.w), mk(FX.w, FY.w, FZ.w), r, inv) & on & valid(3)};
+            // (one slot's test: column c of the six plane rows)
+            auto slot = [&](auto form, float nx, float ny, float nz, float fx, float fy, float fz, int c) {
+                return slab_nf_lanes<decltype(form)::value>(mk(nx, ny, nz), mk(fx, fy, fz), r, inv) & on & valid(c);
+            };
+            auto slots = [&](auto form, unsigned long long (&m)[4]) {
+                m[0] = slot(form, NX.x, NY.x, NZ.x, FX.x, FY.x, FZ.x, 0);
+                m[1] = slot(form, NX.y, NY.y, NZ.y, FX.y, FY.y, FZ.y, 1);
+                m[2] = slot(form, NX.z, NY.z, NZ.z, FX.z, FY.z, FZ.z, 2);
+                m[3] = slot(form, NX.w, NY.w, NZ.w, FX.w, FY.w, FZ.w, 3);
+            };
+            unsigned long long m[4];
+            if constexpr (!PBR_SLAB_FOLD) {
+                slots(std::false_type{}, m);
+            } else if (fold) {
+                slots(std::true_type{}, m);
+            } else {
+                // The exact form beside the folded one runs as a rolled loop over the columns.  Written
+                // straight-line like the folded block, the 48 products (plane − o) · inv the two share
+                // are hoisted above the branch and all live at it: every kernel that walks packets took
+                // four to six VGPRs more, and level 0, at its limit, spilled one more.  Non-foldable rays
+                // are rare (a ±0 or denormal direction component, or a scene with an unordered box).
+                m[0] = m[1] = m[2] = m[3] = 0ull;
+#pragma unroll 1
+                for (int c = 0; c < 4; ++c) {
+                    auto col = [c](float4 v) { return c == 0 ? v.x : (c == 1 ? v.y : (c == 2 ? v.z : v.w)); };   // scalars: uniform
+                    const unsigned long long v = slot(std::false_type{}, col(NX), col(NY), col(NZ), col(FX), col(FY), col(FZ), c);
+                    m[0] = c == 0 ? v : m[0]; m[1] = c == 1 ? v : m[1]; m[2] = c == 2 ? v : m[2]; m[3] = c == 3 ? v : m[3];
+                }
+            }
             // The four masks brought into visit order by three wave-uniform swaps (pbr_quad_order.h:
             // quad_slots' swaps on the live lanes' common signs; any hit: build order), so `first` and
             // the pushes test fixed positions and only a pushed or entered slot needs its column.
@@ -741,7 +799,7 @@ __device__ bool traverse_packet(const DeviceScene& S, Ray& r, HitRec* h, f3 inv,
                 fr = mk(n0 ? lo.x : hi.x, n1 ? lo.y : hi.y, n2 ? lo.z : hi.z);
             }
             const __attribute__((address_space(4))) float* rf = (const __attribute__((address_space(4))) float*)(size_t)(wf + 24);
-            unsigned long long a = m & slab_nf_lanes(nr, fr, r, inv);
+            unsigned long long a = m & ((PBR_SLAB_FOLD && fold) ? slab_nf_lanes<true>(nr, fr, r, inv) : slab_nf_lanes<false>(nr, fr, r, inv));
             if (ANY) a &= __builtin_amdgcn_ballot_w64(alive);
             if (a != 0ull) {
                 act = a;
@@ -766,14 +824,22 @@ __device__ bool traverse_wave(const DeviceScene& S, Ray& r, HitRec* h, bool live
     bool n0 = inv.x < 0, n1 = inv.y < 0, n2 = inv.z < 0;
     const bool ok = live && S.nNodes > 0 && node_hit(S.nodes[0], S.nodes[1], r, inv, n0, n1, n2);   // the root first
     unsigned long long left = __builtin_amdgcn_ballot_w64(ok);
-    if constexpr (ANY) return left ? traverse_packet<true>(S, r, h, inv, n0, n1, n2, ok, 0, 0, 0) : false;
-    const int cls = (int)n0 | ((int)n1 << 1) | ((int)n2 << 2);
+    // PBR_SLAB_FOLD: a lane whose ray may not take the folded slab test
+    const bool exact = PBR_SLAB_FOLD ? slab_needs_exact(S, r, inv) : true;
+    if constexpr (ANY) {
+        if (!left) return false;
+        if (PBR_SLAB_FOLD && __builtin_amdgcn_ballot_w64(ok && exact) == 0ull)
+            return traverse_packet<true>(S, r, h, inv, n0, n1, n2, ok, 0, 0, 0, true);
+        return traverse_packet<true>(S, r, h, inv, n0, n1, n2, ok, 0, 0, 0);
+    }
+    // the class of a lane: its sign octant and, in bit 3, that its ray needs the exact slab test
+    const int cls = (int)n0 | ((int)n1 << 1) | ((int)n2 << 2) | (PBR_SLAB_FOLD ? (int)exact << 3 : 0);
     bool found = false;
     while (left) {
         const int c = __builtin_amdgcn_readlane(cls, __ffsll((long long)left) - 1);
         const bool mine = ok && cls == c;
         left &= ~__builtin_amdgcn_ballot_w64(mine);
-        const bool f = traverse_packet<false>(S, r, h, inv, n0, n1, n2, mine, c & 1, (c >> 1) & 1, (c >> 2) & 1);
+        const bool f = traverse_packet<false>(S, r, h, inv, n0, n1, n2, mine, c & 1, (c >> 1) & 1, (c >> 2) & 1, PBR_SLAB_FOLD && !(c & 8));
         if (mine) found = f;
     }
     return found;
@@ -808,7 +874,12 @@ __device__ bool traverse(const DeviceScene& S, Ray& r, HitRec* h, Counters* c) {
     // binary layout, whose one-entry-per-level stack holds BVHAccel's 64 levels.  Same primitive
     // tests in the same order either way.
     if constexpr (!STATS && kQuadTraversal) {
-        if (SHORT > 0 || !S.binaryWalk) return traverse_quad<ANY, SHORT>(S, r, h, inv, n0, n1, n2);
+        if (SHORT > 0 || !S.binaryWalk) {
+            // PBR_SLAB_FOLD_LANE: the folded slab test where every lane walking here may take it
+            if (PBR_SLAB_FOLD_LANE && __builtin_amdgcn_ballot_w64(slab_needs_exact(S, r, inv)) == 0ull)
+                return traverse_quad<ANY, SHORT, true>(S, r, h, inv, n0, n1, n2);
+            return traverse_quad<ANY, SHORT>(S, r, h, inv, n0, n1, n2);
+        }
     }
     int stackRef[kTraversalStack - SHORT];
     float stackT[kTraversalStack - SHORT];

@@ -1136,6 +1136,7 @@ DeviceScene device_scene(pbr_hip_ctx* ctx) {
     S.rootRef = h.rootRef;
     S.quad = (const float4*)ctx->dQuad.p;
     S.quadRootRef = h.quadRootRef;
+    S.slabExact = h.slabExact ? 1 : 0;
     S.binaryWalk = h.quadStackNeed > kQuadStackLimit ? 1 : 0;
     S.triVerts = (const float4*)ctx->dTri.p;
     S.guard = (int*)ctx->dGuard.p;

@@ -84,6 +84,7 @@ struct DeviceScene {
     const float4* nodes;
     const float4* wide;            // 4 float4 per interior node: child boxes, child refs, axis
     int rootRef;
+    int slabExact;                 // 1: some valid quad slot's box is not finite and ordered — no folded slab test (pbr_slab.h)
     const float4* quad;            // 8 float4 per quad node (two binary levels, pbr_scene.cpp build_quad_nodes)
     int quadRootRef;
     int binaryWalk;                // 1: the quad walk's stack could overflow in this tree (megakernel, binary walk)

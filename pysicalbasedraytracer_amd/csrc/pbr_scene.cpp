@@ -9,6 +9,7 @@
 // identical.
 #include "pbr_scene.h"
 #include "pbr_shading_frame.h"
+#include "pbr_slab.h"
 #include "pbr_material.h"
 #include "pbr_sobol_jk.h"
 #include "pbr_temporal.h"
@@ -75,6 +76,7 @@ void build_quad_nodes(HostScene* S, Ref&& binRef) {
     S->quad.clear();
     S->quadRootRef = binRef(0);
     S->quadStackNeed = 0;
+    S->slabExact = false;
     if (L.empty() || L[0].nPrimitives > 0) return;
     std::vector<int32_t> qid(L.size(), -1);
     int nQuad = 0;
@@ -142,6 +144,8 @@ void build_quad_nodes(HostScene* S, Ref&& binRef) {
     }
     S->quadStackNeed = need[qid[0]];
     S->quadRootRef = qid[0];
+    // the scene's half of the folded slab test's guarantee, whoever built the tree
+    S->slabExact = !slab_scene_foldable(S->quad.data(), (size_t)nQuad);
 }
 
 // The same tree re-laid out for traversal: each interior node carries both children's boxes (so a

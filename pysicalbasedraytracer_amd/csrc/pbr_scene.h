@@ -54,6 +54,7 @@ struct HostScene {
     int32_t rootRef = 0;
     std::vector<float> quad;                // 32 floats per quad node (build_quad_nodes)
     int32_t quadRootRef = 0;
+    bool slabExact = false;                 // some valid quad slot's box is not finite with lo <= hi (pbr_slab.h)
     std::vector<float> primBounds;          // 6 floats (lo, hi) per primitive in prims order: GeometricPrimitive::WorldBound
     std::vector<int32_t> slotOf;            // prims index → BVH slot
     // traversal stack entries the tree can need at most (pbr_layout.h kTraversalStack): the binary

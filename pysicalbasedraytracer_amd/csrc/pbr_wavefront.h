@@ -299,6 +299,7 @@ __device__ void traverse_stream(const DeviceScene& S, int n, int segCap, Load lo
     Ray r;
     f3 inv = mk(0, 0, 0);
     bool n0 = false, n1 = false, n2 = false;
+    bool exact = false;          // PBR_SLAB_FOLD_LANE: the lane's ray may not take the folded slab test
     HitRec h;
     h.slot = -1; h.b0 = h.b1 = h.b2 = 0.f;
     unsigned long long laneSteps = 0, waveSteps = 0;
@@ -329,6 +330,7 @@ __device__ void traverse_stream(const DeviceScene& S, int n, int segCap, Load lo
                         inv = ANY ? mk(1.f / r.d.x, 1.f / r.d.y, 1.f / r.d.z) : mk(1 / r.d.x, 1 / r.d.y, 1 / r.d.z);
                         n0 = inv.x < 0; n1 = inv.y < 0; n2 = inv.z < 0;
                         ok = node_hit(rootA, rootB, r, inv, n0, n1, n2);
+                        if constexpr (PBR_SLAB_FOLD_LANE) exact = slab_needs_exact(S, r, inv);
                     }
                     if (ok) {
                         cur = S.quadRootRef;
@@ -378,7 +380,9 @@ __device__ void traverse_stream(const DeviceScene& S, int n, int segCap, Load lo
             }
         } else {
             QuadSlots q;
-            quad_slots<ANY, NF>(S, cur, r, inv, n0, n1, n2, &q);
+            // (only lanes with a ray in flight are here: the ballot is over them)
+            if (PBR_SLAB_FOLD_LANE && __builtin_amdgcn_ballot_w64(exact) == 0ull) quad_slots<ANY, NF, true>(S, cur, r, inv, n0, n1, n2, &q);
+            else quad_slots<ANY, NF>(S, cur, r, inv, n0, n1, n2, &q);
             const float tM = r.tMax;
             const bool p0 = q.k[0] && q.t[0] < tM, p1 = q.k[1] && q.t[1] < tM, p2 = q.k[2] && q.t[2] < tM,
                        p3 = q.k[3] && q.t[3] < tM;

@@ -6,6 +6,7 @@ On bench.py's C2 (1920x1080, 64 spp, Halton) and C3 (256 spp, Sobol) scenes ever
 the other,
   plain/parent   pbr_hip_render of a library built from the parent commit (--parent; skipped without it)
   plain          pbr_hip_render of this build
+  features/parent  the same feature pass of the parent's library (--parent; skipped without it)
   features       one pbr_hip_render_aov pass over the frame's full sample count, image included
 A variant's time is the host clock around `steps` calls queued back to back on one stream, ending in a
 synchronise, divided by `steps`.  The rounds alternate the variants, so drift of the machine reaches all
@@ -47,6 +48,8 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=0, help="the budget (0: the config's benchmark budget)")
+    ap.add_argument("--normals", action="store_true",
+                    help="the scenes on the stand-in mesh carrying its analytic per-vertex normals")
     ap.add_argument("--json")
     ap.add_argument("--md", help="write the result lines as a markdown document")
     a = ap.parse_args()
@@ -68,27 +71,34 @@ def main():
     out = {"rounds": a.rounds, "steps": a.steps, "width": a.width, "height": a.height, "configs": {}}
     ok = True
     for cfg in a.configs:
-        scene, rd = scenes.CONFIGS[cfg](a.width, a.height, a.spp) if a.spp else scenes.CONFIGS[cfg](a.width, a.height)
+        size = (a.width, a.height, a.spp) if a.spp else (a.width, a.height)
+        if a.normals:   # the kernels' NRM instantiations (k_aov<true, ...>, k_wf_shade<true, ...>)
+            P, I, N = scenes.dragon_standin(normals=True)
+            scene, rd = scenes.CONFIGS[cfg](*size, mesh=(P, I, "standin:displaced-uv-sphere-224"))
+            scene.shapes[0].N = capi.fptr(N)
+            scene._keep.append(N)
+        else:
+            scene, rd = scenes.CONFIGS[cfg](*size)
         npx = a.width * a.height
         budget = HipRenderer.sample_budget(rd)
         rgb = torch.empty((npx, 3), dtype=torch.float32, device=dev)
         rgba = torch.empty((npx, 4), dtype=torch.uint8, device=dev)
         acc = torch.empty((npx, capi.AOV_CHANNELS), dtype=torch.float32, device=dev)
         img = torch.empty((npx, capi.AOV_CHANNELS), dtype=torch.float32, device=dev)
-        names = (["plain/parent"] if parent else []) + ["plain", "features"]
+        names = (["plain/parent"] if parent else []) + ["plain"] + (["features/parent"] if parent else []) + ["features"]
         times = {n: [] for n in names}
-        ref = None
+        ref = ref_feat = None
         st = stream.cuda_stream
 
         def call(r, name):
-            if name == "features":
+            if name.startswith("features"):
                 r.render_aov(rd, 0, budget, acc.data_ptr(), img.data_ptr(), stream=st)
             else:
                 r.render_device(rd, rgb.data_ptr(), rgba.data_ptr(), stream=st, sync=False)
 
         for rnd in range(a.rounds):
             for name in names:
-                r = renderer(parent if name == "plain/parent" else this, scene)   # one context at a time
+                r = renderer(parent if name.endswith("/parent") else this, scene)   # one context at a time
                 rgb.fill_(float("nan"))
                 torch.cuda.synchronize(dev)
                 call(r, name)   # warm-up: code objects, lane buffers
@@ -102,24 +112,29 @@ def main():
                 ms = (time.perf_counter() - t0) / a.steps * 1e3
                 times[name].append(ms)
                 same = True
-                if name != "features":   # this build computes what the parent computed
+                if name.startswith("features"):   # this build computes what the parent computed
+                    bits = img.cpu().numpy().view(np.uint32)
+                    if ref_feat is None:
+                        ref_feat = bits.copy()
+                    same = np.array_equal(bits, ref_feat)
+                else:
                     bits = rgb.cpu().numpy().view(np.uint32)
                     if ref is None:
                         ref = bits.copy()
                     same = np.array_equal(bits, ref)
-                print(f"{cfg} round {rnd} {name:13s} {ms:10.3f} ms{'' if same else '  IMAGE DIFFERS'}", flush=True)
+                print(f"{cfg} round {rnd} {name:15s} {ms:10.3f} ms{'' if same else '  IMAGE DIFFERS'}", flush=True)
                 r.close()
                 if not same:
-                    sys.exit(f"{cfg} {name}: the plain image differs between the builds or the rounds")
+                    sys.exit(f"{cfg} {name}: the image differs between the builds or the rounds")
         res = {}
         for name in names:
             t = times[name]
             res[name] = {"median_ms": statistics.median(t), "min_ms": min(t), "max_ms": max(t),
                          "spread": (max(t) - min(t)) / statistics.median(t), "ms": t}
-        say(f"RESULT {cfg} ({a.width}x{a.height}, {budget} spp, {a.rounds} rounds of {a.steps} calls)")
+        say(f"RESULT {cfg} ({a.width}x{a.height}, {budget} spp, {a.rounds} rounds of {a.steps} calls{', per-vertex normals' if a.normals else ''})")
         for name in names:
             v = res[name]
-            say(f"RESULT {cfg} {name:13s} median {v['median_ms']:10.3f} ms (min {v['min_ms']:.3f}, max {v['max_ms']:.3f}, "
+            say(f"RESULT {cfg} {name:15s} median {v['median_ms']:10.3f} ms (min {v['min_ms']:.3f}, max {v['max_ms']:.3f}, "
                 f"spread {100 * v['spread']:.2f}%)")
         if parent:
             p, t = res["plain/parent"], res["plain"]
@@ -129,6 +144,9 @@ def main():
             ok = ok and slower <= bound
             say(f"RESULT {cfg} (a) plain vs parent: {100 * slower:+.2f}% (bound: the larger spread, {100 * bound:.2f}%) {verdict}")
             res["plain_vs_parent"] = {"slower": slower, "bound": bound, "pass": slower <= bound}
+            p, t = res["features/parent"], res["features"]   # reported; no speed is required of the pass
+            say(f"RESULT {cfg} features vs parent: {100 * (t['median_ms'] / p['median_ms'] - 1):+.2f}% "
+                f"(the larger spread: {100 * max(p['spread'], t['spread']):.2f}%)")
         # (b) one profiled run of each: the feature kernel beside the plain frame's camera kernel
         r = renderer(this, scene)
         r.set_profiling(True)

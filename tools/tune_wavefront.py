@@ -18,9 +18,21 @@ sys.path.insert(0, ROOT)
 from pysicalbasedraytracer_amd import HipRenderer, capi, scenes, tiles_for_rank  # noqa: E402
 
 
+def config_c2_point(width=1920, height=1080, spp=64):
+    """C2's dragon and mirror floor under a point light instead of the SkyBox: the level-0 instantiations
+    of frames without a SkyBox (k_wf_shade<*, 5, true, 4, true, false, *>).  Not a BASELINE config."""
+    s = scenes.Scene()
+    scenes._dragon(s, s.matte((0.0, 1.0, 0.0)))
+    Pf, If = scenes.quad(-1.12, 40.0)
+    s.mesh(Pf, If, s.mirror((1.0, 1.0, 1.0)))
+    s.point_light((0.0, 4.0, 4.0), (20.0, 20.0, 20.0))
+    cam = scenes.camera(width, height, (0.0, 0.55, 2.6), (0.0, -0.25, 0.0))
+    return s, scenes.render_desc(cam, capi.INTEGRATOR_WHITTED, spp, 5)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="C2")
+    ap.add_argument("--config", default="C2", help="a scenes.CONFIGS name, or C2P: C2 under a point light, no SkyBox")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--lib", default=None, help="an experimental build of libpbr_hip.so")
     ap.add_argument("--shard", default=None, help="R/N: render only rank R's tiles of an N-GPU job "
@@ -38,7 +50,7 @@ def main():
     if a.lib:
         capi._lib = capi.load_library(a.lib)
     print("build:", capi.load_library().pbr_hip_build_info().decode(), flush=True)
-    scene, rd = scenes.CONFIGS[a.config]()
+    scene, rd = dict(scenes.CONFIGS, C2P=config_c2_point)[a.config]()
     W, H, spp = rd.camera.width, rd.camera.height, rd.spp
     npx = W * H
     if a.shard:
