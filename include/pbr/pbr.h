@@ -752,6 +752,11 @@ struct DenoiseParams {
     float sigmaL = 4.f;        // edge stopping on luminance against the local variance, ...
     float sigmaN = 0.4f;       // ... on the mean shading normal, ...
     float sigmaZ = 1.f;        // ... on the distance against its screen-space slope; +inf switches a term off
+    // The spatial variance estimate before level 0 (pbr_spatial_variance of pbr_hip.h; 0: off).  A pixel with
+    // fewer than spatialMinCount (2..64, suggested 4) samples takes its variance from the (2·spatialRadius+1)²
+    // pixels around it (radius 1..3), so an image of one sample per pixel can be filtered.
+    int spatialMinCount = 0;
+    int spatialRadius = 1;
 };
 class SamplerIntegrator : public Integrator {
   public:
@@ -792,7 +797,8 @@ class SamplerIntegrator : public Integrator {
     // The edge-avoiding à-trous filter (no reference counterpart; pbr_hip_denoise) over what RenderSamples
     // and RenderFeatures have accumulated on the device: the filtered image of the RenderSamples samples
     // done so far goes to the FrameBuffer, flipped as Render writes it.  The sums are left as they are, so
-    // passes may continue.  Throws std::invalid_argument when RenderSamples has done fewer than 2 samples or
+    // passes may continue.  Throws std::invalid_argument when RenderSamples has done fewer than 2 samples (with
+    // params.spatialMinCount > 0, the spatial variance estimate: fewer than 1) or
     // RenderFeatures none (a RenderAdaptive image cannot be filtered: its counts are not kept), when
     // SetTiles or SetDevices is in force, or for parameters out of range.  Synchronous.
     void Denoise(const DenoiseParams& params = DenoiseParams());

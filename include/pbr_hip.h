@@ -24,6 +24,9 @@
  *   pbr_hip_render_aov    — (none): per-pixel albedo, coverage, normal and depth of the first surface the
  *                           same camera samples see, in the same resumable passes (feature buffers)
  *   pbr_hip_denoise       — (none): an edge-avoiding à-trous filter over those sums and feature buffers
+ *   pbr_hip_denoise_sv    — (none): that filter with a spatial variance estimate before its first level, so
+ *                           that pixels with one sample are filtered (pbr_hip_spatial_variance_host: the
+ *                           estimate on the CPU)
  *   pbr_hip_temporal      — (none): the previous frame's sums reprojected into this frame's (temporal
  *                           accumulation; pbr_hip_camera_matrices gives it a camera's matrices)
  *   pbr_hip_destroy      — scene/integrator destructors
@@ -485,6 +488,37 @@ typedef struct pbr_denoise {
 } pbr_denoise;
 int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const int32_t* counts, const float* accum,
                     const float* aov, float* rgb_out, uint8_t* rgba_out, float* var_out, void* stream);
+
+/* ---- the denoiser's spatial variance estimate (no reference counterpart) ----
+ * pbr_hip_denoise forms a pixel's variance from its own two sums, so a pixel with one sample has none
+ * (V = 0) and the luminance edge-stop drops every neighbour that is not equal: a 1-sample frame comes back
+ * as it went in.  The estimate (SVGF, Schied et al. 2017, §4.2) runs between prepare and level 0: a pixel
+ * with 1 <= count < min_count takes its variance from the first and second moments of the pixels in a
+ * (2·radius+1)² window around it, each weighted by its count times the filter's normal and depth edge-stops
+ * at step 1 (no luminance term), as the variance of a mean of its own `count` samples; a pixel whose kept
+ * neighbours hold fewer than two samples, and every pixel with count 0 or >= min_count, keeps prepare's
+ * variance.  The colour is not changed; the levels and the finish run as in pbr_hip_denoise.  Float32 in the
+ * order DESIGN §4.9 states, pinned bit for bit by tests/spatial_variance_expected.py.
+ *
+ * pbr_hip_denoise_sv: sv == NULL is pbr_hip_denoise in every respect (which is a call of it).  With sv,
+ * counts == NULL with samples == 1 is allowed; everything else — buffers, outputs, ordering, streams — is as
+ * for pbr_hip_denoise.  The estimate needs a fifth working plane (16 bytes per pixel), allocated by the
+ * first call that passes sv.
+ * PBR_E_INVALID: as pbr_hip_denoise, but with sv samples < 1 (not < 2) when counts == NULL; min_count outside
+ * 2..64; radius outside 1..3.
+ *
+ * pbr_hip_spatial_variance_host: prepare and the estimate — the device's per-pixel functions compiled for
+ * the host — over host pointers; var_out, 1 float per pixel (required), is the variance plane level 0 would
+ * read.  sv == NULL gives prepare's variance.  No context, no GPU call; the same refusals. */
+typedef struct pbr_spatial_variance {
+    int min_count;  /* 2..64: a pixel with 1 <= count < min_count takes the spatial estimate; suggested 4 */
+    int radius;     /* 1..3: the window is (2·radius+1)² pixels; suggested 1 */
+} pbr_spatial_variance;
+int pbr_hip_denoise_sv(pbr_hip_ctx* ctx, const pbr_denoise* p, const pbr_spatial_variance* sv, int samples,
+                       const int32_t* counts, const float* accum, const float* aov, float* rgb_out, uint8_t* rgba_out,
+                       float* var_out, void* stream);
+int pbr_hip_spatial_variance_host(const pbr_denoise* p, const pbr_spatial_variance* sv, int samples, const int32_t* counts,
+                                  const float* accum, const float* aov, float* var_out);
 
 /* ---- temporal accumulation (no reference counterpart) ----
  * The temporal part of SVGF (Schied et al. 2017) as a merge of accumulators: the previous frame's sums are

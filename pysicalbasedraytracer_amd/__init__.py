@@ -188,9 +188,9 @@ class HipRenderer:
                     "render_aov")
 
     @staticmethod
-    def _check_denoise(who, width, height, samples, have_counts, iterations, sigma_l, sigma_n, sigma_z):
+    def _check_denoise(who, width, height, samples, have_counts, iterations, sigma_l, sigma_n, sigma_z, min_samples=2):
         """The frame and filter parameters of a denoise call, refused before any library call; returns
-        them as a capi.Denoise (demodulate left 0)."""
+        them as a capi.Denoise (demodulate left 0).  min_samples: 1 with the spatial variance estimate."""
         width, height, samples, iterations = int(width), int(height), int(samples), int(iterations)
         if width < 1 or height < 1:
             raise ValueError(f"{who}: width and height must be >= 1")
@@ -201,12 +201,30 @@ class HipRenderer:
         for name, v in (("sigma_l", sigma_l), ("sigma_n", sigma_n), ("sigma_z", sigma_z)):
             if not float(v) > 0.0:   # (a NaN fails the comparison)
                 raise ValueError(f"{who}: {name} must be > 0 (inf switches the term off)")
-        if not have_counts and samples < 2:
+        if not have_counts and samples < 2 and min_samples >= 2:
             raise ValueError(f"{who}: samples must be >= 2 (a variance needs two), or give per-pixel counts")
+        if not have_counts and samples < 1:
+            raise ValueError(f"{who}: samples must be >= 1, or give per-pixel counts")
         return capi.Denoise(width, height, iterations, 0, float(sigma_l), float(sigma_n), float(sigma_z))
 
+    @staticmethod
+    def _check_spatial(who, spatial):
+        """spatial=(min_count, radius) of a denoise call, refused before any library call; returns it as a
+        capi.SpatialVariance."""
+        try:
+            min_count, radius = spatial
+            min_count, radius = int(min_count), int(radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: spatial must be (min_count, radius) or None") from None
+        if not 2 <= min_count <= 64:
+            raise ValueError(f"{who}: spatial min_count must be 2..64")
+        if not 1 <= radius <= 3:
+            raise ValueError(f"{who}: spatial radius must be 1..3")
+        return capi.SpatialVariance(min_count, radius)
+
     def denoise(self, width, height, samples, accum_ptr, aov_ptr, rgb_ptr=None, rgba_ptr=None, var_ptr=None, counts_ptr=None,
-                iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0, stream: int | None = None):
+                iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0, stream: int | None = None,
+                spatial=None):
         """The edge-avoiding à-trous filter (pbr_hip_denoise) over a width x height frame in raster order:
         accum_ptr the 6 sums per pixel of render_passes, aov_ptr the 8-float image of render_aov, counts_ptr
         (or None: every pixel took `samples`) the int32 per-pixel sample counts of render_adaptive.
@@ -214,15 +232,55 @@ class HipRenderer:
         luminance against the local variance (sigma_l), the mean normal (sigma_n) and the distance against
         its slope (sigma_z); demodulate filters colour / albedo.  Outputs (device pointers, at least one):
         rgb_ptr 3 float32 per pixel, rgba_ptr its 8-bit film transform, var_ptr the filtered variance.
+        spatial=(min_count, radius), suggested (4, 1): the spatial variance estimate (pbr_hip_denoise_sv) before
+        level 0 — a pixel with 1 <= count < min_count takes its variance from the (2 radius + 1)^2 pixels
+        around it, so frames of one sample per pixel are filtered; samples may then be 1.
         Asynchronous, ordered as render_aov; wait_frame(stream, 0) orders another stream after it."""
-        p = self._check_denoise("denoise", width, height, samples, bool(counts_ptr), iterations, sigma_l, sigma_n, sigma_z)
+        sv = None if spatial is None else self._check_spatial("denoise", spatial)
+        p = self._check_denoise("denoise", width, height, samples, bool(counts_ptr), iterations, sigma_l, sigma_n, sigma_z,
+                                min_samples=2 if sv is None else 1)
         if not accum_ptr or not aov_ptr:
             raise ValueError("denoise: accum (6 float32 per pixel) and aov (8 float32 per pixel) are required")
         if not (rgb_ptr or rgba_ptr or var_ptr):
             raise ValueError("denoise: no output buffer")
         p.demodulate = 1 if demodulate else 0
-        self._check(self.lib.pbr_hip_denoise(self.ctx, C.byref(p), int(samples), counts_ptr or None, accum_ptr, aov_ptr,
-                                             rgb_ptr or None, rgba_ptr or None, var_ptr or None, stream), "denoise")
+        if sv is None:
+            self._check(self.lib.pbr_hip_denoise(self.ctx, C.byref(p), int(samples), counts_ptr or None, accum_ptr, aov_ptr,
+                                                 rgb_ptr or None, rgba_ptr or None, var_ptr or None, stream), "denoise")
+        else:
+            self._check(self.lib.pbr_hip_denoise_sv(self.ctx, C.byref(p), C.byref(sv), int(samples), counts_ptr or None,
+                                                    accum_ptr, aov_ptr, rgb_ptr or None, rgba_ptr or None, var_ptr or None,
+                                                    stream), "denoise")
+
+    def spatial_variance_host(self, width, height, samples, accum, aov, counts=None, spatial=(4, 1), demodulate=True,
+                              sigma_n=0.4, sigma_z=1.0):
+        """The variance plane level 0 of denoise(spatial=...) reads, on the CPU over numpy arrays
+        (pbr_hip_spatial_variance_host: the device's prepare and estimate functions compiled for the host; no GPU
+        call): [n] float32.  spatial=None gives prepare's own variance."""
+        sv = None if spatial is None else self._check_spatial("spatial_variance_host", spatial)
+        p = self._check_denoise("spatial_variance_host", width, height, samples, counts is not None, 1, 1.0, sigma_n, sigma_z,
+                                min_samples=2 if sv is None else 1)
+        n = p.width * p.height
+        arrays = []
+        for name, a, dt, ch in (("accum", accum, np.float32, 6), ("aov", aov, np.float32, 8), ("counts", counts, np.int32, 1)):
+            if a is None:
+                if name != "counts":
+                    raise ValueError(f"spatial_variance_host: {name} is required")
+                arrays.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != n * ch:
+                raise ValueError(f"spatial_variance_host: {name} holds {a.size} values, expected {n} x {ch}")
+            arrays.append(a)
+        acc, img, cnt = arrays
+        p.demodulate = 1 if demodulate else 0
+        out = np.empty(n, np.float32)
+        rc = self.lib.pbr_hip_spatial_variance_host(C.byref(p), None if sv is None else C.byref(sv), int(samples),
+                                                    cnt.ctypes.data if cnt is not None else None, acc.ctypes.data,
+                                                    img.ctypes.data, out.ctypes.data)
+        if rc != capi.PBR_OK:
+            raise PbrError(f"spatial_variance_host failed ({rc})")
+        return out
 
     @staticmethod
     def _check_temporal(who, width, height, samples, have_counts, max_history, tol_z, tol_n, cur, prev):
@@ -639,20 +697,25 @@ class ProgressiveRender:
         f = self._aov_img
         return {"albedo": f[:, 0:3], "coverage": f[:, 3], "normal": f[:, 4:7], "depth": f[:, 7]}
 
-    def denoise(self, iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0):
+    def denoise(self, iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0, spatial=None):
         """The image after the samples done so far, filtered (HipRenderer.denoise over the carried sums
         and the feature image): (rgb [n, 3] float32, rgba [n, 4] uint8) device tensors of its own, reused
-        by the next call.  Needs features=True, at least 2 samples per pixel, and a descriptor without
-        tiles (the filter works on a whole frame in raster order).  Asynchronous as step()."""
+        by the next call.  Needs features=True, at least 2 samples per pixel (1 with spatial=(min_count,
+        radius), the spatial variance estimate), and a descriptor without tiles (the filter works on a whole
+        frame in raster order).  Asynchronous as step()."""
         if not self._features:
             raise ValueError("ProgressiveRender.denoise: constructed with features=False")
         if self.rdesc.n_tiles:
             raise ValueError("ProgressiveRender.denoise: a tiled descriptor (the filter would stop at the tiles' borders)")
-        if self.samples_done < 2:
+        if spatial is not None:
+            HipRenderer._check_spatial("ProgressiveRender.denoise", spatial)
+            if self.samples_done < 1:
+                raise ValueError("ProgressiveRender.denoise needs at least 1 sample per pixel")
+        elif self.samples_done < 2:
             raise ValueError("ProgressiveRender.denoise needs at least 2 samples per pixel")
         w, h = self.rdesc.camera.width, self.rdesc.camera.height
         HipRenderer._check_denoise("ProgressiveRender.denoise", w, h, self.samples_done, False, iterations, sigma_l, sigma_n,
-                                   sigma_z)
+                                   sigma_z, min_samples=2 if spatial is None else 1)
         torch = self._buffers()
         if self._dn_rgb is None:
             self._dn_rgb = torch.empty((self.n_pixels, 3), dtype=torch.float32, device=self._accum.device)
@@ -662,7 +725,7 @@ class ProgressiveRender:
         self.renderer.denoise(w, h, self.samples_done, self._accum.data_ptr(), self._aov_img.data_ptr(),
                               rgb_ptr=self._dn_rgb.data_ptr(), rgba_ptr=self._dn_rgba.data_ptr(), iterations=iterations,
                               demodulate=demodulate, sigma_l=sigma_l, sigma_n=sigma_n, sigma_z=sigma_z,
-                              stream=self._stream.cuda_stream)
+                              stream=self._stream.cuda_stream, spatial=spatial)
         current.wait_stream(self._stream)
         return self._dn_rgb, self._dn_rgba
 
@@ -926,11 +989,15 @@ class TemporalRender:
         acc, cnt, img = self._sets[self._hist]
         return {"accum": acc, "counts": cnt, "features": img, "motion": self._motion}
 
-    def denoise(self, iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0):
+    def denoise(self, iterations=5, demodulate=True, sigma_l=4.0, sigma_n=0.4, sigma_z=1.0, spatial=None):
         """The merged frame filtered (HipRenderer.denoise over the merged sums with counts = the merged
-        counts): (rgb [n, 3] float32, rgba [n, 4] uint8) device tensors of its own."""
+        counts): (rgb [n, 3] float32, rgba [n, 4] uint8) device tensors of its own.  spatial=(min_count,
+        radius): the spatial variance estimate for the pixels whose history is shorter than min_count samples
+        — the first frame, and every disoccluded pixel, at one sample per frame."""
         if self._hist is None:
             raise ValueError("TemporalRender.denoise: no frame yet (or reset)")
+        if spatial is not None:
+            HipRenderer._check_spatial("TemporalRender.denoise", spatial)
         HipRenderer._check_denoise("TemporalRender.denoise", self.width, self.height, 0, True, iterations, sigma_l, sigma_n,
                                    sigma_z)
         torch = self._buffers()
@@ -943,7 +1010,7 @@ class TemporalRender:
         self.renderer.denoise(self.width, self.height, 0, acc.data_ptr(), img.data_ptr(), rgb_ptr=self._dn_rgb.data_ptr(),
                               rgba_ptr=self._dn_rgba.data_ptr(), counts_ptr=cnt.data_ptr(), iterations=iterations,
                               demodulate=demodulate, sigma_l=sigma_l, sigma_n=sigma_n, sigma_z=sigma_z,
-                              stream=self._stream.cuda_stream)
+                              stream=self._stream.cuda_stream, spatial=spatial)
         current.wait_stream(self._stream)
         return self._dn_rgb, self._dn_rgba
 

@@ -303,6 +303,12 @@ class Denoise(C.Structure):
                 ("sigma_l", C.c_float), ("sigma_n", C.c_float), ("sigma_z", C.c_float)]
 
 
+class SpatialVariance(C.Structure):
+    """pbr_spatial_variance: which pixels take the denoiser's spatial variance estimate, and its window
+    (pbr_hip_denoise_sv)."""
+    _fields_ = [("min_count", C.c_int), ("radius", C.c_int)]
+
+
 class Temporal(C.Structure):
     """pbr_temporal: the frame, the merge's parameters and the two cameras' matrices (pbr_hip_temporal)."""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("max_history", C.c_int), ("demodulate", C.c_int),
@@ -417,6 +423,8 @@ EXPORTS = {
                                    C.POINTER(C.c_int)]),
     "pbr_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(Denoise), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pbr_hip_denoise_sv": (C.c_int, [C.c_void_p, C.POINTER(Denoise), C.POINTER(SpatialVariance), C.c_int] + [C.c_void_p] * 7),
+    "pbr_hip_spatial_variance_host": (C.c_int, [C.POINTER(Denoise), C.POINTER(SpatialVariance), C.c_int] + [C.c_void_p] * 4),
     "pbr_hip_camera_matrices": (C.c_int, [C.POINTER(CameraDesc), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                           C.POINTER(C.c_float)]),
     "pbr_hip_temporal": (C.c_int, [C.c_void_p, C.POINTER(Temporal), C.c_int] + [C.c_void_p] * 12),
@@ -466,7 +474,8 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_plan_chunks", "pbr_hip_last_chunks", "pbr_hip_adaptive_select", "pbr_hip_render_passes_list",
                    "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov", "pbr_hip_denoise", "pbr_hip_bsdf",
                    "pbr_hip_bsdf_host", "pbr_hip_phase_hg", "pbr_hip_phase_hg_host", "pbr_hip_shading_host",
-                   "pbr_hip_camera_matrices", "pbr_hip_temporal", "pbr_hip_temporal_host")
+                   "pbr_hip_camera_matrices", "pbr_hip_temporal", "pbr_hip_temporal_host", "pbr_hip_denoise_sv",
+                   "pbr_hip_spatial_variance_host")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

@@ -2,7 +2,8 @@
 // prepare (sums → colour, variance and guides in the filter's domain), `iterations` wavelet levels
 // ping-ponging between two colour planes, finish (remodulate, film transform).  Image-space work on a
 // frame in raster order; no scene, queue or lane is touched.  Included by pbr_kernels.hip after
-// pbr_aov.h.
+// pbr_aov.h.  Prepare's per-pixel arithmetic and the optional spatial variance estimate between prepare
+// and level 0 are the functions of pbr_denoise_rule.h, shared with the host.
 //
 // The rule is float32 in a fixed order, without transcendentals and (the build has -ffp-contract=off)
 // without fused operations, so tests/denoise_expected.py restates it in numpy to the bit.  Both level
@@ -30,6 +31,7 @@ static_assert(kDnLdsLevels >= 0 && kDnLdsLevels <= 3, "LDS variants exist for st
 //   xv {x_r, x_g, x_b, V}     colour and variance in the filter's domain (two planes, ping-pong)
 //   nz {N_x, N_y, N_z, z}     the guides
 //   gb {g, b_r, b_g, b_b}     the depth slope and the demodulation divisor, read once per pixel
+//   un {u_r, u_g, u_b, n}     the per-sample second moment and the count: only for the spatial estimate
 struct DnParams {
     int W, H;
     int nbx;                 // tiles per row of tiles: the grid is 1-D over nbx x nby tiles
@@ -46,53 +48,23 @@ __device__ __forceinline__ void dn_tile_origin(int nbx, int* x0, int* y0) {
     *x0 = (int)(b % (unsigned)nbx) * kDnTW;
     *y0 = (int)(b / (unsigned)nbx) * kDnTH;
 }
-__device__ __forceinline__ int dn_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// Prepare.  k: the pixel's sample count.  Mean and variance of the mean per channel (the adaptive
-// rule's arithmetic), demodulated by the first-hit albedo where a sample hit and by 1 where it missed.
+// Prepare: dn_prepare_pixel (pbr_denoise_rule.h) at the thread's pixel.  U: also write the un plane the
+// spatial estimate reads; a plain denoise call launches the instantiation without it.
+template <bool U>
 __global__ __launch_bounds__(kDnBlock) void k_dn_prepare(int W, int H, int nbx, int samples, int demodulate,
                                                         const int32_t* __restrict__ counts, const float* __restrict__ accum,
                                                         const float* __restrict__ aov, float4* __restrict__ xv,
-                                                        float4* __restrict__ nz, float4* __restrict__ gb) {
+                                                        float4* __restrict__ nz, float4* __restrict__ gb, float4* __restrict__ un) {
     int x0, y0;
     dn_tile_origin(nbx, &x0, &y0);
     const int x = x0 + (int)(threadIdx.x % kDnTW), y = y0 + (int)(threadIdx.x / kDnTW);
     if (x >= W || y >= H) return;
     const size_t p = (size_t)y * W + x;
-    const int k = counts ? counts[p] : samples;
-    const float* a = accum + 6 * p;
-    const float* f = aov + 8 * p;
-    float m[3], v[3], b[3];
-    if (k >= 2) {
-        const float n = (float)k;
-        const float nn = n * (n - 1.f);
-        for (int c = 0; c < 3; ++c) {
-            m[c] = a[c] / n;
-            const float d = a[3 + c] - a[c] * m[c];
-            v[c] = (d > 0.f ? d : 0.f) / nn;
-        }
-    } else {
-        for (int c = 0; c < 3; ++c) {
-            m[c] = k == 1 ? a[c] : 0.f;
-            v[c] = 0.f;
-        }
-    }
-    for (int c = 0; c < 3; ++c) {
-        if (demodulate) {
-            const float al = f[c] + (1.f - f[3]);
-            b[c] = al > 0.01f ? al : 0.01f;
-        } else {
-            b[c] = 1.f;
-        }
-    }
-    const float V = (v[0] / (b[0] * b[0]) + v[1] / (b[1] * b[1])) + v[2] / (b[2] * b[2]);
-    const int xl = dn_clamp(x - 1, W - 1), xr = dn_clamp(x + 1, W - 1), yu = dn_clamp(y - 1, H - 1), yd = dn_clamp(y + 1, H - 1);
-    const float gx = fabsf(aov[8 * ((size_t)y * W + xr) + 7] - aov[8 * ((size_t)y * W + xl) + 7]);
-    const float gy = fabsf(aov[8 * ((size_t)yd * W + x) + 7] - aov[8 * ((size_t)yu * W + x) + 7]);
-    const float g = (gx > gy ? gx : gy) * 0.5f;
-    xv[p] = make_float4(m[0] / b[0], m[1] / b[1], m[2] / b[2], V);
-    nz[p] = make_float4(f[4], f[5], f[6], f[7]);
-    gb[p] = make_float4(g, b[0], b[1], b[2]);
+    const DnPrepared<float4> o = dn_prepare_pixel<U, float4>(W, H, x, y, samples, demodulate, counts, accum, aov);
+    xv[p] = o.xv;
+    nz[p] = o.nz;
+    gb[p] = o.gb;
+    if (U) un[p] = o.un;
 }
 
 // One level at pixel (x, y), step s.  src.xv(qx, qy) / src.nz(qx, qy) give the previous level's planes
@@ -204,6 +176,57 @@ __global__ __launch_bounds__(kDnBlock) void k_dn_atrous_lds(DnParams P) {
     if (x >= P.W || y >= P.H) return;
     const DnLdsSrc<S> src{sxv, snz, ox, oy};
     P.xvOut[(size_t)y * P.W + x] = dn_filter(P, S, x, y, src);
+}
+
+// The spatial variance estimate, between prepare and level 0: dn_estimate
+// (pbr_denoise_rule.h) at the thread's pixel over the tile and its halo of R pixels staged in LDS, three
+// planes (xv, un, nz).  Halo pixels outside the frame are not loaded and never read.  {x, V'} goes to the
+// other colour plane, so no launch reads a word it writes.  A tile none of whose pixels takes the
+// estimate (every count 0 or >= minCount) copies its pixels and stages nothing.
+template <int R>
+struct DnSpatialSrc {
+    static constexpr int LW = kDnTW + 2 * R, LH = kDnTH + 2 * R;
+    const float4* sxv;
+    const float4* sun;
+    const float4* snz;
+    int ox, oy;   // the frame position of LDS element (0, 0)
+    __device__ __forceinline__ float4 xv(int qx, int qy) const { return sxv[(qy - oy) * LW + (qx - ox)]; }
+    __device__ __forceinline__ float4 un(int qx, int qy) const { return sun[(qy - oy) * LW + (qx - ox)]; }
+    __device__ __forceinline__ float4 nz(int qx, int qy) const { return snz[(qy - oy) * LW + (qx - ox)]; }
+};
+template <int R>
+__global__ __launch_bounds__(kDnBlock) void k_dn_spatial(DnParams P, const float4* __restrict__ un, int minCount) {
+    constexpr int LW = DnSpatialSrc<R>::LW, LH = DnSpatialSrc<R>::LH;
+    __shared__ float4 sxv[LW * LH];
+    __shared__ float4 sun[LW * LH];
+    __shared__ float4 snz[LW * LH];
+    int x0, y0;
+    dn_tile_origin(P.nbx, &x0, &y0);
+    const int x = x0 + (int)(threadIdx.x % kDnTW), y = y0 + (int)(threadIdx.x / kDnTW);
+    const bool inside = x < P.W && y < P.H;
+    const size_t p = inside ? (size_t)y * P.W + x : 0;
+    float n = 0.f;
+    if (inside) n = un[p].w;
+    if (!__syncthreads_or(n >= 1.f && n < (float)minCount)) {
+        if (inside) P.xvOut[p] = P.xvIn[p];
+        return;
+    }
+    const int ox = x0 - R, oy = y0 - R;
+    for (int e = threadIdx.x; e < LW * LH; e += kDnBlock) {
+        const int gx = ox + e % LW, gy = oy + e / LW;
+        if (gx >= 0 && gx < P.W && gy >= 0 && gy < P.H) {
+            const size_t q = (size_t)gy * P.W + gx;
+            sxv[e] = P.xvIn[q];
+            sun[e] = un[q];
+            snz[e] = P.nz[q];
+        }
+    }
+    __syncthreads();
+    if (!inside) return;
+    const DnSpatialSrc<R> src{sxv, sun, snz, ox, oy};
+    float4 c = src.xv(x, y);
+    c.w = dn_estimate<R>(P.W, P.H, x, y, minCount, P.in, P.iz, P.gb[p].x, src);
+    P.xvOut[p] = c;
 }
 
 // Finish: back out of the filter's domain, the film transform, the filtered variance.

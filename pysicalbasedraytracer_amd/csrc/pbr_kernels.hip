@@ -27,6 +27,7 @@
 #include "pbr_aov_plan.h"
 #include "pbr_probe_glue.h"
 #include "pbr_temporal.h"
+#include "pbr_denoise_rule.h"
 
 using namespace pbr;
 
@@ -991,6 +992,7 @@ struct pbr_hip_ctx {
     DevBuf dTexels, dTextures, dTexMats;   // ImageTextures and the textured materials' parameters
     DevBuf dAlbedo;                        // per material: the feature buffers' albedo (pbr_aov.h)
     DevBuf dDnXV[2], dDnNZ, dDnGB;         // the denoiser's working planes (pbr_denoise.h), 16 B per pixel each
+    DevBuf dDnUN;                          // ... and the fifth, which only the spatial estimate needs
     DevBuf dNodes, dWide, dQuad, dTri, dInfo, dUV, dTriN, dSph, dMat, dLights, dEnv, dCdf, dFunc, dMedia;
     DevBuf dPrimes, dRecips, dPrimeSums, dPerms, dPrimIds;
     DevBuf dSobol, dSobolHi, dSobolPix;  // active Sobol nibble tables (index bits 0-31, 32-51), pixel tables
@@ -2901,16 +2903,17 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
 // ---- denoise (pbr_denoise.h)
 int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const int32_t* counts, const float* accum,
                     const float* aov, float* rgb_out, uint8_t* rgba_out, float* var_out, void* stream) {
+    return pbr_hip_denoise_sv(ctx, p, nullptr, samples, counts, accum, aov, rgb_out, rgba_out, var_out, stream);
+}
+
+// sv: the spatial variance estimate between prepare and level 0 (NULL: none, the plain call's launches)
+int pbr_hip_denoise_sv(pbr_hip_ctx* ctx, const pbr_denoise* p, const pbr_spatial_variance* sv, int samples, const int32_t* counts,
+                       const float* accum, const float* aov, float* rgb_out, uint8_t* rgba_out, float* var_out, void* stream) {
     if (!ctx) return PBR_E_INVALID;
     if (!p) return set_err(ctx, PBR_E_INVALID, "denoise: null parameters");
     if (!accum || !aov) return set_err(ctx, PBR_E_INVALID, "denoise: accum (6 floats per pixel) and aov (8 floats per pixel) are required");
     if (!rgb_out && !rgba_out && !var_out) return set_err(ctx, PBR_E_INVALID, "denoise: no output");
-    if (p->width < 1 || p->height < 1) return set_err(ctx, PBR_E_INVALID, "denoise: width and height must be >= 1");
-    if ((long long)p->width * p->height >= (1ll << 31)) return set_err(ctx, PBR_E_INVALID, "denoise: width * height must be below 2^31");
-    if (p->iterations < 1 || p->iterations > 8) return set_err(ctx, PBR_E_INVALID, "denoise: iterations must be 1..8");
-    if (!(p->sigma_l > 0.f) || !(p->sigma_n > 0.f) || !(p->sigma_z > 0.f))
-        return set_err(ctx, PBR_E_INVALID, "denoise: sigma_l, sigma_n and sigma_z must be > 0");
-    if (!counts && samples < 2) return set_err(ctx, PBR_E_INVALID, "denoise: samples must be >= 2 (or give per-pixel counts)");
+    if (const char* what = dn_params_error(p, sv, samples, counts)) return set_err(ctx, PBR_E_INVALID, what);
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     // the working planes are the context's: as a pass, a call on another stream drains the context first
@@ -2927,6 +2930,10 @@ int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const i
         HIP_TRY(ctx->dDnNZ.ensure(plane));
         HIP_TRY(ctx->dDnGB.ensure(plane));
     }
+    if (sv && ctx->dDnUN.bytes < plane) {   // the fifth plane: only a call with the estimate allocates it
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(ctx->dDnUN.ensure(plane));
+    }
     float4* xv[2] = {(float4*)ctx->dDnXV[0].p, (float4*)ctx->dDnXV[1].p};
     float4* nz = (float4*)ctx->dDnNZ.p;
     float4* gb = (float4*)ctx->dDnGB.p;
@@ -2934,10 +2941,13 @@ int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const i
     const dim3 grid((unsigned)((long long)nbx * nby)), blk(kDnBlock);   // (below 2^31 tiles: npx is)
     ctx->batchFrames = 0;   // (set when the call is queued)
     begin_lanes(ctx, s);
+    float4* un = sv ? (float4*)ctx->dDnUN.p : nullptr;
     PROF_LAUNCH(KP_DN_PREPARE, s,
-        hipLaunchKernelGGL(k_dn_prepare, grid, blk, 0, s, W, H, nbx, samples, p->demodulate ? 1 : 0, counts, accum, aov, xv[0], nz, gb));
+        if (sv) hipLaunchKernelGGL(k_dn_prepare<true>, grid, blk, 0, s, W, H, nbx, samples, p->demodulate ? 1 : 0, counts, accum, aov, xv[0], nz, gb, un);
+        else hipLaunchKernelGGL(k_dn_prepare<false>, grid, blk, 0, s, W, H, nbx, samples, p->demodulate ? 1 : 0, counts, accum, aov, xv[0], nz, gb, un));
     prof_host(ctx, KP_DN_PREPARE, 0, (unsigned long long)npx);
     if (counts) prof_host(ctx, KP_DN_PREPARE, 1, (unsigned long long)npx);
+    if (sv) prof_host(ctx, KP_DN_PREPARE, 2, (unsigned long long)npx);
     DnParams D;
     std::memset(&D, 0, sizeof(D));
     D.W = W;
@@ -2948,10 +2958,22 @@ int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const i
     D.iz = 1.f / (p->sigma_z * p->sigma_z);
     D.nz = nz;
     D.gb = gb;
+    int first = 0;   // the colour plane level 0 reads
+    if (sv) {        // the estimate writes {x, V'} to the other plane: the levels start from there
+        D.step = 1;
+        D.xvIn = xv[0];
+        D.xvOut = xv[1];
+        PROF_LAUNCH(KP_DN_SPATIAL, s,
+            if (sv->radius == 1) hipLaunchKernelGGL(k_dn_spatial<1>, grid, blk, 0, s, D, (const float4*)un, sv->min_count);
+            else if (sv->radius == 2) hipLaunchKernelGGL(k_dn_spatial<2>, grid, blk, 0, s, D, (const float4*)un, sv->min_count);
+            else hipLaunchKernelGGL(k_dn_spatial<3>, grid, blk, 0, s, D, (const float4*)un, sv->min_count));
+        prof_host(ctx, KP_DN_SPATIAL, 0, (unsigned long long)npx);
+        first = 1;
+    }
     for (int i = 0; i < p->iterations; ++i) {
         D.step = 1 << i;
-        D.xvIn = xv[i & 1];
-        D.xvOut = xv[(i & 1) ^ 1];
+        D.xvIn = xv[(i + first) & 1];
+        D.xvOut = xv[((i + first) & 1) ^ 1];
         const int lds = i < kDnLdsLevels ? D.step : 0;
         PROF_LAUNCH(KP_DN_LEVEL0 + i, s,
             if (lds == 1) hipLaunchKernelGGL(k_dn_atrous_lds<1>, grid, blk, 0, s, D);
@@ -2962,7 +2984,7 @@ int pbr_hip_denoise(pbr_hip_ctx* ctx, const pbr_denoise* p, int samples, const i
     }
     PROF_LAUNCH(KP_DN_FINISH, s,
         hipLaunchKernelGGL(k_dn_finish, dim3((unsigned)((npx + kDnBlock - 1) / kDnBlock)), blk, 0, s, npx,
-                           (const float4*)xv[p->iterations & 1], (const float4*)gb, rgb_out, (uint32_t*)rgba_out, var_out));
+                           (const float4*)xv[(p->iterations + first) & 1], (const float4*)gb, rgb_out, (uint32_t*)rgba_out, var_out));
     HIP_TRY(hipGetLastError());
     prof_host(ctx, KP_DN_FINISH, 0, (unsigned long long)npx);
     if (rgb_out) prof_host(ctx, KP_DN_FINISH, 1, (unsigned long long)npx);
@@ -3117,7 +3139,7 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         "k_wfp_camera_extend", "k_wfp_shade", "k_wfp_shadow", "k_wfp_probe", "k_wfp_resolve", "k_wfp_finish",
         "k_wfv_shade", "k_wfv_tr", "k_wfv_resolve", "k_render", "k_wf_shade_l0", "k_aov", "k_aov_tex",
         "k_dn_prepare", "k_dn_atrous_l0", "k_dn_atrous_l1", "k_dn_atrous_l2", "k_dn_atrous_l3", "k_dn_atrous_l4",
-        "k_dn_atrous_l5", "k_dn_atrous_l6", "k_dn_atrous_l7", "k_dn_finish", "k_tp_accumulate"};
+        "k_dn_atrous_l5", "k_dn_atrous_l6", "k_dn_atrous_l7", "k_dn_finish", "k_tp_accumulate", "k_dn_spatial"};
     unsigned long long c[KP_COUNT][kProfFields];
     std::memset(c, 0, sizeof(c));
     if (ctx->profOn) HIP_TRY(hipMemcpy(c, ctx->dProf.p, sizeof(c), hipMemcpyDeviceToHost));
@@ -3164,7 +3186,11 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         // the denoiser, f[0] pixels.  prepare: sums 24 + features 32 (+ 4 per count, f[1]) read, three
         // planes written; a level: colour and guides read, colour written; finish: colour and divisor
         // read, f[1] rgb, f[2] rgba and f[3] variance pixels written
-        case KP_DN_PREPARE: return 104 * f[0] + 4 * f[1];
+        // (f[2] pixels: the un plane written as well, for the spatial estimate)
+        case KP_DN_PREPARE: return 104 * f[0] + 4 * f[1] + 16 * f[2];
+        // the spatial estimate, f[0] pixels: colour, moments and guides read, the slope (4), colour written;
+        // halo reads hit in L2 and are not counted
+        case KP_DN_SPATIAL: return 68 * f[0];
         case KP_DN_FINISH: return 32 * f[0] + 12 * f[1] + 4 * f[2] + 4 * f[3];
         // the temporal merge, f[0] pixels: this frame's sums 24 + features 32 read, the previous frame's sums,
         // features and counts (60, each entry once: the four taps of neighbouring pixels overlap) read, sums

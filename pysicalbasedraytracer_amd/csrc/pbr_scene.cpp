@@ -13,6 +13,7 @@
 #include "pbr_material.h"
 #include "pbr_sobol_jk.h"
 #include "pbr_temporal.h"
+#include "pbr_denoise_rule.h"
 #include "pbr_xform.h"
 
 #include <algorithm>
@@ -956,6 +957,53 @@ extern "C" int pbr_hip_temporal_host(const pbr_temporal* p, int samples, const i
             for (int c = 0; c < 6; ++c) accum_out[6 * q + c] = o.s[c];
             counts_out[q] = o.count;
             if (motion_out) { motion_out[2 * q] = o.mx; motion_out[2 * q + 1] = o.my; }
+        }
+    return PBR_OK;
+}
+
+// pbr_hip_spatial_variance_host: dn_prepare_pixel and dn_estimate (pbr_denoise_rule.h) over host buffers, on
+// the CPU: the variance plane level 0 of the denoiser would read
+namespace {
+struct DnHostSrc {
+    const pbr::DnHost4* pxv;
+    const pbr::DnHost4* pun;
+    const pbr::DnHost4* pnz;
+    int W;
+    const pbr::DnHost4& xv(int qx, int qy) const { return pxv[(size_t)qy * W + qx]; }
+    const pbr::DnHost4& un(int qx, int qy) const { return pun[(size_t)qy * W + qx]; }
+    const pbr::DnHost4& nz(int qx, int qy) const { return pnz[(size_t)qy * W + qx]; }
+};
+}  // namespace
+extern "C" int pbr_hip_spatial_variance_host(const pbr_denoise* p, const pbr_spatial_variance* sv, int samples,
+                                             const int32_t* counts, const float* accum, const float* aov, float* var_out) {
+    using namespace pbr;
+    if (dn_params_error(p, sv, samples, counts)) return PBR_E_INVALID;
+    if (!accum || !aov || !var_out) return PBR_E_INVALID;
+    const int W = p->width, H = p->height;
+    const size_t npx = (size_t)W * H;
+    std::vector<DnHost4> xv(npx), un(npx), nz(npx);
+    std::vector<float> g(npx);
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const DnPrepared<DnHost4> o = dn_prepare_pixel<true, DnHost4>(W, H, x, y, samples, p->demodulate ? 1 : 0, counts, accum, aov);
+            const size_t q = (size_t)y * W + x;
+            xv[q] = o.xv;
+            un[q] = o.un;
+            nz[q] = o.nz;
+            g[q] = o.gb.x;
+        }
+    const float in = 1.f / (p->sigma_n * p->sigma_n), iz = 1.f / (p->sigma_z * p->sigma_z);
+    const DnHostSrc src{xv.data(), un.data(), nz.data(), W};
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const size_t q = (size_t)y * W + x;
+            float V = xv[q].w;
+            if (sv) {
+                if (sv->radius == 1) V = dn_estimate<1>(W, H, x, y, sv->min_count, in, iz, g[q], src);
+                else if (sv->radius == 2) V = dn_estimate<2>(W, H, x, y, sv->min_count, in, iz, g[q], src);
+                else V = dn_estimate<3>(W, H, x, y, sv->min_count, in, iz, g[q], src);
+            }
+            var_out[q] = V;
         }
     return PBR_OK;
 }

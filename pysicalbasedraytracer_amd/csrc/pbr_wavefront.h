@@ -45,6 +45,7 @@ enum ProfKind {
     // the denoiser (pbr_denoise.h): prepare, one family per wavelet level (8 of them), finish
     KP_DN_PREPARE, KP_DN_LEVEL0, KP_DN_FINISH = KP_DN_LEVEL0 + 8,
     KP_TP_ACCUMULATE,   // the temporal merge (pbr_temporal.h)
+    KP_DN_SPATIAL,      // the denoiser's spatial variance estimate (pbr_denoise.h), appended: the kinds above keep their indices
     KP_COUNT
 };
 constexpr int kProfFields = 8;

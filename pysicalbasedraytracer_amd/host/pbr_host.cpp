@@ -1660,9 +1660,14 @@ void SamplerIntegrator::Denoise(const DenoiseParams& params) {
     if (!tiles.empty())
         throw std::invalid_argument(who + ": SetTiles is in force (the filter works on a whole frame, not across tile borders)");
     if (!devices.empty()) throw std::invalid_argument(who + ": one device (SetDevice), not SetDevices");
-    if (!prog || samplesDone < 2)
+    const bool spatial = params.spatialMinCount != 0;
+    if (spatial && (params.spatialMinCount < 2 || params.spatialMinCount > 64))
+        throw std::invalid_argument(who + ": spatialMinCount must be 0 (off) or 2..64");
+    if (spatial && (params.spatialRadius < 1 || params.spatialRadius > 3))
+        throw std::invalid_argument(who + ": spatialRadius must be 1..3");
+    if (!prog || samplesDone < (spatial ? 1 : 2))
         throw std::invalid_argument(who + ": RenderSamples has accumulated " + std::to_string(prog ? samplesDone : 0) +
-                                    " samples; a variance needs 2");
+                                    (spatial ? " samples; the spatial variance estimate needs 1" : " samples; a variance needs 2"));
     if (!feat || featuresDone < 1) throw std::invalid_argument(who + ": RenderFeatures has accumulated no samples");
     const int W = pixelBounds.pMax.x, H = pixelBounds.pMax.y;
     const size_t npx = (size_t)W * H;
@@ -1672,8 +1677,9 @@ void SamplerIntegrator::Denoise(const DenoiseParams& params) {
     const pbr_denoise p = {W, H, params.iterations, params.demodulate ? 1 : 0, params.sigmaL, params.sigmaN, params.sigmaZ};
     float* dRgb = (float*)prog->p[1];
     uint8_t* dRgba = (uint8_t*)prog->p[2];
-    check(ctx, pbr_hip_denoise(ctx, &p, samplesDone, nullptr, (const float*)prog->p[0], (const float*)feat->p[1], dRgb, dRgba,
-                               nullptr, nullptr), "pbr_hip_denoise");
+    const pbr_spatial_variance sv = {params.spatialMinCount, params.spatialRadius};
+    check(ctx, pbr_hip_denoise_sv(ctx, &p, spatial ? &sv : nullptr, samplesDone, nullptr, (const float*)prog->p[0],
+                                  (const float*)feat->p[1], dRgb, dRgba, nullptr, nullptr), "pbr_hip_denoise");
     check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
     std::vector<float> rgb(npx * 3);
     std::vector<uint8_t> rgba(npx * 4);
