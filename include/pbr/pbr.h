@@ -793,7 +793,11 @@ class SamplerIntegrator : public Integrator {
     // firstSample == 0 starts, any other value must continue where the last RenderFeatures call ended
     // (its count is independent of RenderSamples').  Honours SetTiles: pixels outside the tiles are left 0.
     // Synchronous, single device; a custom (table) sampler throws.
-    void RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out);
+    // mirrorBounces = B > 0 (pbr_hip_render_aov_mirrors): up to B mirror bounces are followed and the
+    // surface at the end of the chain is recorded, with the product of the albedos along the chain, its
+    // own normal and the summed distance; every pass onto one set of sums must use the same value.
+    // Outside 0..16: std::invalid_argument.
+    void RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out, int mirrorBounces = 0);
     // The edge-avoiding à-trous filter (no reference counterpart; pbr_hip_denoise) over what RenderSamples
     // and RenderFeatures have accumulated on the device: the filtered image of the RenderSamples samples
     // done so far goes to the FrameBuffer, flipped as Render writes it.  The sums are left as they are, so

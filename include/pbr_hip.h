@@ -23,6 +23,9 @@
  *                           pbr_hip_adaptive_select and pbr_hip_render_passes_list are its two steps)
  *   pbr_hip_render_aov    — (none): per-pixel albedo, coverage, normal and depth of the first surface the
  *                           same camera samples see, in the same resumable passes (feature buffers)
+ *   pbr_hip_render_aov_mirrors — (none): that pass with mirror bounces followed, so that a mirror records the
+ *                           surface it reflects at the unfolded distance (pbr_hip_mirror_step_host: one
+ *                           step on the CPU)
  *   pbr_hip_denoise       — (none): an edge-avoiding à-trous filter over those sums and feature buffers
  *   pbr_hip_denoise_sv    — (none): that filter with a spatial variance estimate before its first level, so
  *                           that pixels with one sample are filtered (pbr_hip_spatial_variance_host: the
@@ -457,6 +460,36 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int first_
  * (either may be NULL when max_launches == 0); *n_launches is their total number. */
 int pbr_hip_plan_aov(int64_t n_pixels, int samples, int max_launches, int64_t* first_pixel, int64_t* n_launch_pixels,
                      int* n_launches);
+/* The feature pass with mirror bounces followed, so that a mirror reports what it reflects.
+ * max_bounces == 0 is pbr_hip_render_aov in every respect (that call is this one with 0); outside 0..16:
+ * PBR_E_INVALID.  Buffers, passes, tiles, streams, ordering, the crossing guard and the other refusals are
+ * those of pbr_hip_render_aov.  Per sample, with max_bounces = B > 0:
+ *   The chain.  The camera ray is traced as above, through material-less surfaces, to a hit with a BSDF:
+ *   surface 1.  At surface j a mirror step is taken when j <= B, the material is PBR_MAT_MIRROR, and
+ *   Whitted's SpecularReflect would continue there: Sample_f of the specular reflection lobe on the hit's
+ *   frame (ss = normalize(dpdu), ts = cross(ns, ss)) gives a non-black f (Kr after its texture and clamp is
+ *   not all zero), pdf > 0 (wo is not in the shading tangent plane) and absdot(wi, ns) != 0.  The lobe is
+ *   deterministic, wi = (-wo.x, -wo.y, wo.z) in that frame, and no sampler dimension is read, so the chain
+ *   is that of Whitted, Path and VolPath alike.  Glass and glossy lobes are not followed.
+ *   The continuation is SpawnRay(isect, wi) (pbr_hip_mirror_step_host gives its bits; pbr_hip_bsdf with
+ *   PBR_BSDF_MIRROR reports the direction as s_wi), traced again through material-less surfaces; the
+ *   1024-crossing bound counts over the whole chain.
+ *   The recorded surface is the last surface with a BSDF the chain reached: the first one where no step is
+ *   taken (not a mirror, the step refused, or B steps taken), or, when a continuation misses the scene, the
+ *   mirror it left (crossings made after that mirror do not count towards its distance).
+ *   The eight values (all 0 when the camera ray itself misses):
+ *     0-2  a = alb_1; a = a * alb_2; ... per channel, float32, in chain order up to and including the
+ *          recorded surface; each alb is the albedo defined above at that hit (a mirror's: Kr)
+ *     3    1.0f
+ *     4-6  ns of the recorded surface, world space, as the intersection leaves it.  It is NOT reflected
+ *          back through the mirrors: in a planar mirror it is the normal of the real surface, not of its
+ *          mirror image
+ *     7    T at the recorded surface, T = T + t over every segment up to it, in order, float32
+ * For a planar mirror eye + d * T is the mirror image of the recorded point, which is the point whose
+ * reprojection pbr_hip_temporal needs; for a curved mirror the chain is followed all the same, but that
+ * identity does not hold.  Sums, passes, the image formula and the launch plan are unchanged. */
+int pbr_hip_render_aov_mirrors(pbr_hip_ctx* ctx, const pbr_render_desc* desc, int max_bounces, int first_sample, int samples,
+                               float* accum, float* aov_out);
 
 /* ---- denoise (no reference counterpart) ----
  * An edge-avoiding à-trous filter (Dammertz et al. 2010; the spatial part of SVGF, Schied et al. 2017)
@@ -815,6 +848,12 @@ int pbr_hip_bsdf(pbr_hip_ctx* ctx, int variant, int n, const pbr_bsdf_query* que
  * mask that does not cover the material's lobes. */
 int pbr_hip_bsdf_host(const pbr_material_desc* material, int variant, int n, const pbr_bsdf_query* queries,
                       pbr_bsdf_record* out);
+/* One mirror step of pbr_hip_render_aov_mirrors per hit, through the function its kernel calls, compiled
+ * for the host.  hits: records as pbr_hip_query leaves them (p, p_error, n, ns, dpdu, wo and the two media
+ * are read); kr: the mirror's Kr at each hit, 3 floats, textures evaluated and clamped.  followed[i]: 1 when
+ * the step is taken, and rays_out + 7 * i is then the continuation (o.xyz, d.xyz, tMax = inf); else 0 and
+ * seven zeros.  No context, no GPU.  PBR_E_INVALID: a NULL argument or n < 0. */
+int pbr_hip_mirror_step_host(int n, const pbr_surface_hit* hits, const float* kr, float* rays_out, int32_t* followed);
 /* HenyeyGreenstein::p and Sample_p (Media/Medium.h:24-27, Medium.cpp:9-26) as VolPath's shade calls
  * them: queries = g, wo.xyz, wi.xyz, u0, u1 (9 floats); out = p(wo, wi), the sampled wi.xyz and its
  * value (5 floats).  The _host form runs the same source on the CPU. */

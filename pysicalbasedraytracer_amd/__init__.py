@@ -173,7 +173,14 @@ class HipRenderer:
         self._check(self.lib.pbr_hip_render_passes(self.ctx, C.byref(d), first_sample, samples_per_pass, n, accum_ptr,
                                                    self._ptr_array(rgb_ptrs), self._ptr_array(rgba_ptrs)), "render_passes")
 
-    def render_aov(self, rdesc, first_sample, samples, accum_ptr, out_ptr=None, stream: int | None = None):
+    @staticmethod
+    def _check_mirror_bounces(who, mirror_bounces) -> int:
+        b = int(mirror_bounces)
+        if b < 0 or b > capi.AOV_MAX_MIRROR_BOUNCES:
+            raise ValueError(f"{who}: mirror_bounces must be in 0..{capi.AOV_MAX_MIRROR_BOUNCES}")
+        return b
+
+    def render_aov(self, rdesc, first_sample, samples, accum_ptr, out_ptr=None, stream: int | None = None, mirror_bounces=0):
         """A feature pass (pbr_hip_render_aov): for samples [first_sample, first_sample + samples) of every
         pixel, the albedo (3), hit (1), shading normal (3) and distance (1) of the first surface the camera
         sample sees, added in sample order onto accum (device, capi.AOV_CHANNELS float32 per pixel, packed
@@ -181,11 +188,25 @@ class HipRenderer:
         receives the image over all samples so far: mean albedo, coverage, mean normal (not renormalised),
         mean distance of the samples that hit.  rdesc.spp stays the whole budget; the descriptor's
         integrator, depth and light strategy are not read.  Asynchronous, ordered as render_passes;
-        wait_frame(stream, 0) orders another stream after it."""
+        wait_frame(stream, 0) orders another stream after it.
+        mirror_bounces = B > 0 (pbr_hip_render_aov_mirrors): up to B mirror bounces are followed, and the
+        surface at the end of the chain is recorded, with the product of the albedos along the chain, its own
+        normal (not reflected back) and the summed distance; 0 is the plain pass."""
+        b = self._check_mirror_bounces("render_aov", mirror_bounces)
         first_sample, samples, _, _ = self._check_pass("render_aov", rdesc, first_sample, samples, 1, accum_ptr, 8)
         d = self._device_desc(rdesc, stream)
-        self._check(self.lib.pbr_hip_render_aov(self.ctx, C.byref(d), first_sample, samples, accum_ptr, out_ptr or None),
-                    "render_aov")
+        if b == 0:   # (the plain entry point: the same call underneath, and an older A/B build has it)
+            rc = self.lib.pbr_hip_render_aov(self.ctx, C.byref(d), first_sample, samples, accum_ptr, out_ptr or None)
+        else:
+            rc = self.lib.pbr_hip_render_aov_mirrors(self.ctx, C.byref(d), b, first_sample, samples, accum_ptr, out_ptr or None)
+        self._check(rc, "render_aov")
+
+    def mirror_step_host(self, hits, kr):
+        """One mirror step of the followed feature pass per hit, on the CPU (pbr_hip_mirror_step_host: the
+        kernel's own function compiled for the host; no GPU call): hits an array of capi.SurfaceHit as query()
+        returns them, kr [n, 3] the mirror's Kr at each.  Returns (rays [n, 7] float32: o, d, tMax of the
+        continuation, zeros where the step is refused; followed [n] int32)."""
+        return capi.mirror_step_host(hits, kr, self.lib)
 
     @staticmethod
     def _check_denoise(who, width, height, samples, have_counts, iterations, sigma_l, sigma_n, sigma_z, min_samples=2):
@@ -626,9 +647,12 @@ class ProgressiveRender:
 
     features=True: every step also advances a feature accumulator ([n_pixels, 8] float32, the sums of
     HipRenderer.render_aov) over the same samples; features() gives the denoiser inputs, and state() /
-    restore() carry it under the key "features"."""
+    restore() carry it under the key "features".  mirror_bounces=B: those feature passes follow up to B
+    mirror bounces (render_aov's mirror_bounces).  The state does not record B: restoring a state taken under
+    another mirror_bounces continues sums of a different rule, and is the caller's error (not detected)."""
 
-    def __init__(self, renderer: HipRenderer, rdesc, device=None, features=False):
+    def __init__(self, renderer: HipRenderer, rdesc, device=None, features=False, mirror_bounces=0):
+        self.mirror_bounces = HipRenderer._check_mirror_bounces("ProgressiveRender", mirror_bounces)
         self.budget = HipRenderer._pass_budget("ProgressiveRender", rdesc)
         if rdesc.spp < 1:
             raise ValueError("ProgressiveRender: rdesc.spp (the sample budget) must be >= 1")
@@ -680,7 +704,8 @@ class ProgressiveRender:
                                     stream=self._stream.cuda_stream)
         if self._features:   # (one feature pass over the step's samples, behind its passes on the same stream)
             self.renderer.render_aov(self.rdesc, self.samples_done, n_samples * passes, self._aov.data_ptr(),
-                                     self._aov_img.data_ptr(), stream=self._stream.cuda_stream)
+                                     self._aov_img.data_ptr(), stream=self._stream.cuda_stream,
+                                     mirror_bounces=self.mirror_bounces)
         current.wait_stream(self._stream)
         self.samples_done += n_samples * passes
         return self._rgb, self._rgba
@@ -894,10 +919,13 @@ class TemporalRender:
     of the previous call, and that call's camera) into them, and keeps the result as the new history.
     Owns the sums ([n, 6] float32), counts ([n] int32) and feature images ([n, 8] float32) as torch tensors
     on the renderer's device, in raster order: the descriptor must have no tiles.  The scene is static;
-    after a new upload call reset()."""
+    after a new upload call reset().  mirror_bounces=B: the feature pass of every frame follows up to B
+    mirror bounces (render_aov's mirror_bounces), so that what a planar mirror shows is reprojected with the
+    parallax of its mirror image instead of the mirror's own."""
 
     def __init__(self, renderer: HipRenderer, rdesc, samples_per_frame, cycle=16, max_history=32, demodulate=True,
-                 tol_z=0.05, tol_n=0.1, device=None):
+                 tol_z=0.05, tol_n=0.1, device=None, mirror_bounces=0):
+        self.mirror_bounces = HipRenderer._check_mirror_bounces("TemporalRender", mirror_bounces)
         k, cycle = int(samples_per_frame), int(cycle)
         if k < 1 or cycle < 1:
             raise ValueError("TemporalRender: samples_per_frame and cycle must be >= 1")
@@ -966,7 +994,7 @@ class TemporalRender:
             if self._hist is None:
                 hcnt.zero_()   # (no history: a count of 0 drops every tap)
         r.render_passes(d, s0, k, acc.data_ptr(), [None], [None], stream=st.cuda_stream)
-        r.render_aov(d, s0, k, self._aov_sum.data_ptr(), None, stream=st.cuda_stream)
+        r.render_aov(d, s0, k, self._aov_sum.data_ptr(), None, stream=st.cuda_stream, mirror_bounces=self.mirror_bounces)
         with torch.cuda.stream(st):   # the feature image over these k samples (aov_out's formula)
             f = self._aov_sum
             img[:, 0:7] = f[:, 0:7] / torch.full_like(f[:, 0:7], float(k))   # (a tensor divisor: a true division)

@@ -282,6 +282,7 @@ def plan_chunks(integrator, n_pixels, spp, max_depth, n_lights=1, sky_light=Fals
 
 
 AOV_CHANNELS = 8   # PBR_AOV_CHANNELS: albedo rgb, hit, shading normal xyz, t
+AOV_MAX_MIRROR_BOUNCES = 16   # pbr_hip_render_aov_mirrors: max_bounces lies in 0..16
 
 
 def plan_aov(n_pixels, samples, lib=None) -> list:
@@ -364,6 +365,26 @@ def bsdf_host(material: "MaterialDesc", variant, queries, lib=None):
     return out
 
 
+def mirror_step_host(hits, kr, lib=None):
+    """pbr_hip_mirror_step_host: the followed feature pass's mirror step, compiled for the CPU.  hits: a
+    ctypes array (or list) of SurfaceHit; kr: [n, 3] float32.  Returns (rays [n, 7] float32, followed [n]
+    int32)."""
+    import numpy as np
+    n = len(hits)
+    arr = hits if isinstance(hits, C.Array) else (SurfaceHit * max(1, n))(*hits)
+    k = np.ascontiguousarray(kr, dtype=np.float32).reshape(-1, 3)
+    if k.shape[0] != n:
+        raise ValueError(f"mirror_step_host: {k.shape[0]} kr for {n} hits")
+    if n == 0:
+        k = np.zeros((1, 3), dtype=np.float32)   # (the library refuses NULL whatever n is)
+    rays = np.zeros((max(1, n), 7), dtype=np.float32)
+    followed = np.zeros(max(1, n), dtype=np.int32)
+    rc = (lib or load_library()).pbr_hip_mirror_step_host(n, arr, k.ctypes.data, rays.ctypes.data, followed.ctypes.data)
+    if rc != PBR_OK:
+        raise ValueError(f"mirror_step_host: refused ({rc})")
+    return rays[:n], followed[:n]
+
+
 def phase_hg_host(queries, lib=None):
     """pbr_hip_phase_hg_host: [n, 9] (g, wo, wi, u0, u1) → [n, 5] (p, sampled wi, its value)."""
     import numpy as np
@@ -419,6 +440,8 @@ EXPORTS = {
     "pbr_hip_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.POINTER(Adaptive), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.POINTER(AdaptiveResult)]),
     "pbr_hip_render_aov": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pbr_hip_render_aov_mirrors": (C.c_int, [C.c_void_p, C.POINTER(RenderDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "pbr_hip_mirror_step_host": (C.c_int, [C.c_int, C.POINTER(SurfaceHit), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pbr_hip_plan_aov": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                    C.POINTER(C.c_int)]),
     "pbr_hip_denoise": (C.c_int, [C.c_void_p, C.POINTER(Denoise), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -475,7 +498,7 @@ OPTIONAL_FOR_AB = ("pbr_hip_sync", "pbr_hip_set_profiling", "pbr_hip_get_profile
                    "pbr_hip_render_adaptive", "pbr_hip_render_aov", "pbr_hip_plan_aov", "pbr_hip_denoise", "pbr_hip_bsdf",
                    "pbr_hip_bsdf_host", "pbr_hip_phase_hg", "pbr_hip_phase_hg_host", "pbr_hip_shading_host",
                    "pbr_hip_camera_matrices", "pbr_hip_temporal", "pbr_hip_temporal_host", "pbr_hip_denoise_sv",
-                   "pbr_hip_spatial_variance_host")
+                   "pbr_hip_spatial_variance_host", "pbr_hip_render_aov_mirrors", "pbr_hip_mirror_step_host")
 
 
 def load_library(path: str | None = None) -> C.CDLL:

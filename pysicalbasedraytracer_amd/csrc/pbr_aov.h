@@ -16,6 +16,7 @@
 #pragma once
 
 constexpr int kAovChannels = PBR_AOV_CHANNELS;
+constexpr int kAovMaxBounces = 16;   // pbr_hip_render_aov_mirrors' max_bounces (Whitted's kWfMaxDepth levels)
 constexpr int kAovPitch = kAovBlock + 1;
 static_assert(kAovChannels == 8, "a thread's (pixel, channel) is (t >> 3, t & 7)");
 
@@ -26,7 +27,8 @@ struct AovParams {
     long long pix0, pixEnd;   // this launch's packed pixels [pix0, pixEnd)
     float* accum;             // 8 floats per packed pixel of the frame: the carried sums
     float* out;               // the image (8 floats per pixel), or null
-    const float4* albedo;     // per material: material_albedo of its constants, w = 1 if it has a BSDF
+    const float4* albedo;     // per material: material_albedo of its constants, w = its pbr_material_type (0: no BSDF)
+    int maxBounces;           // FOLLOW: the mirror steps a sample's chain may take (1..16)
 };
 
 // The one texture a textured material's albedo reads, through its UVMapping2D, then the material's
@@ -46,13 +48,28 @@ __device__ __forceinline__ void aov_tex_albedo(const TexMat* texMats, const TexD
 // the interaction of the hit (hit_isect: sphere and triangle), and at the 64 registers of 8 waves that
 // spills: compiled at each bound, untextured / textured packet-walk instantiation, VGPRs spilled →
 // scratch bytes per lane: 8 waves 15 → 64 / 20 → 80, 7 waves 8 → 48 / 10 → 48, 6 waves 4 → 32 / 4 → 32,
-// 5 waves (93 VGPRs) 0 → 0.  Five it is: no scratch (profiles/aov_resource_usage.md).
+// 5 waves 0 → 0.  Five it is (profiles/aov_resource_usage.md).  As compiled today at that bound
+// (profiles/aov_follow_resource_usage.md): 91 VGPRs untextured and 95 textured, no scratch; the NRM
+// instantiations (per-vertex normals, added since) 96 VGPRs with 4 spilled, 32 scratch bytes per lane.
 constexpr int kAovOcc = 5;
+// The FOLLOW instantiations carry seven more values across the walk (the record: albedo product, ns, T):
+// at 5 waves the packet-walk ones spill 1 (untextured) to 6 VGPRs, 16-32 scratch bytes per lane, touched once
+// per chain surface and not inside the walk; at 4 waves none (profiles/aov_follow_resource_usage.md).
+#ifndef PBR_AOV_FOLLOW_OCC
+#define PBR_AOV_FOLLOW_OCC 5
+#endif
+constexpr int kAovFollowOcc = PBR_AOV_FOLLOW_OCC;
 
 // TEX: the scene has image textures (else their evaluation is compiled out, as make_bsdf<TEX>);
-// BINARY: the scene runs the per-lane binary walk (DeviceScene::binaryWalk), whose stack is scratch
-template <bool NRM, bool TEX, bool BINARY>
-__global__ __launch_bounds__(256, kAovOcc) void k_aov(AovParams A) {
+// BINARY: the scene runs the per-lane binary walk (DeviceScene::binaryWalk), whose stack is scratch;
+// FOLLOW: mirror bounces are followed (pbr_hip_render_aov_mirrors with max_bounces > 0).
+// A followed chain stays inside the walk loop, as a crossing does: at every surface with a BSDF the lane
+// forms the interaction, multiplies the albedo in, and keeps (albedo product, ns, T) as its record; a
+// Mirror there, below the bound, replaces the ray by mirror_step's and the lane stays pending, while
+// lanes whose chains ended keep their record under the mask.  A continuation that misses leaves the
+// record of the mirror it left.
+template <bool NRM, bool TEX, bool BINARY, bool FOLLOW = false>
+__global__ __launch_bounds__(256, FOLLOW ? kAovFollowOcc : kAovOcc) void k_aov(AovParams A) {
     __shared__ float tile[kAovChannels * kAovPitch];
     __shared__ float sums[kAovChannels * kAovBlock];
     const KParams& P = A.P;
@@ -90,6 +107,12 @@ __global__ __launch_bounds__(256, kAovOcc) void k_aov(AovParams A) {
         bool pending = live, hit = false;
         float tsum = 0.f;
         int crossings = 0, mat = -1;
+        // FOLLOW: the record of the last surface with a BSDF the chain reached (recA doubles as the running product)
+        float recA[3] = {0.f, 0.f, 0.f};
+        f3 recNs = mk(0, 0, 0);
+        float recT = 0.f;
+        int steps = 0;
+        bool have = false;
         HitRec h;
         h.slot = -1; h.b0 = h.b1 = h.b2 = 0.f;
         while (__builtin_amdgcn_ballot_w64(pending) != 0ull) {
@@ -111,12 +134,35 @@ __global__ __launch_bounds__(256, kAovOcc) void k_aov(AovParams A) {
                         if (++crossings > kMaxPassThrough) {
                             atomicOr(S.guard, kGuardWhittedPassThrough);
                             hit = false;
+                            have = false;
                         } else {
                             Isect cross;
                             hit_isect<NRM>(S, h, r, &cross);
                             tsum = tsum + r.tMax;
                             r = spawn_ray(cross, r.d);
                             again = true;
+                        }
+                    } else if constexpr (FOLLOW) {
+                        Isect si;
+                        hit_isect<NRM>(S, h, r, &si);
+                        const float4 a = A.albedo[mat];
+                        float al[3] = {a.x, a.y, a.z};
+                        if constexpr (TEX) {
+                            if (S.texMats) aov_tex_albedo(S.texMats, S.textures, S.texels, mat, si.u, si.v, al);
+                        }
+                        if (have) { recA[0] = recA[0] * al[0]; recA[1] = recA[1] * al[1]; recA[2] = recA[2] * al[2]; }
+                        else { recA[0] = al[0]; recA[1] = al[1]; recA[2] = al[2]; }
+                        have = true;
+                        recNs = si.sn;
+                        tsum = tsum + r.tMax;
+                        recT = tsum;
+                        if (steps < A.maxBounces && a.w == (float)PBR_MAT_MIRROR) {
+                            Ray next;
+                            if (mirror_step(si, sp3(al[0], al[1], al[2]), &next)) {
+                                r = next;
+                                ++steps;
+                                again = true;
+                            }
                         }
                     }
                 }
@@ -126,7 +172,12 @@ __global__ __launch_bounds__(256, kAovOcc) void k_aov(AovParams A) {
         float alb[3] = {0.f, 0.f, 0.f};
         f3 ns = mk(0, 0, 0);
         float t = 0.f;
-        if (hit) {
+        if constexpr (FOLLOW) {
+            hit = have;   // (a continuation that missed leaves the record of the mirror it left)
+            alb[0] = recA[0]; alb[1] = recA[1]; alb[2] = recA[2];
+            ns = recNs;
+            t = recT;
+        } else if (hit) {
             Isect si;
             hit_isect<NRM>(S, h, r, &si);
             const float4 a = A.albedo[mat];

@@ -94,6 +94,35 @@ int pbr_hip_bsdf_host(const pbr_material_desc* material, int variant, int n, con
     return PBR_OK;
 }
 
+// mirror_step (pbr_device.h), the step k_aov's FOLLOW instantiations take, on caller-given hits
+int pbr_hip_mirror_step_host(int n, const pbr_surface_hit* hits, const float* kr, float* rays_out, int32_t* followed) {
+    if (n < 0 || !hits || !kr || !rays_out || !followed) return PBR_E_INVALID;
+    for (int i = 0; i < n; ++i) {
+        const pbr_surface_hit& h = hits[i];
+        Isect it;
+        it.p = mk(h.p[0], h.p[1], h.p[2]);
+        it.pError = mk(h.p_error[0], h.p_error[1], h.p_error[2]);
+        it.wo = mk(h.wo[0], h.wo[1], h.wo[2]);
+        it.n = mk(h.n[0], h.n[1], h.n[2]);
+        it.sn = mk(h.ns[0], h.ns[1], h.ns[2]);
+        it.dpdu = mk(h.dpdu[0], h.dpdu[1], h.dpdu[2]);
+        it.slot = -1;
+        it.medIn = h.medium_inside;
+        it.medOut = h.medium_outside;
+        it.u = h.uv[0];
+        it.v = h.uv[1];
+        Ray next = mkray(mk(0, 0, 0), mk(0, 0, 0), 0.f, -1);
+        const bool ok = mirror_step(it, sp3(kr[3 * i], kr[3 * i + 1], kr[3 * i + 2]), &next);
+        if (!ok) next = mkray(mk(0, 0, 0), mk(0, 0, 0), 0.f, -1);
+        float* o = rays_out + (size_t)7 * i;
+        o[0] = next.o.x; o[1] = next.o.y; o[2] = next.o.z;
+        o[3] = next.d.x; o[4] = next.d.y; o[5] = next.d.z;
+        o[6] = next.tMax;
+        followed[i] = ok ? 1 : 0;
+    }
+    return PBR_OK;
+}
+
 int pbr_hip_phase_hg(pbr_hip_ctx* ctx, int n, const float* queries, float* out) {
     if (!ctx || n < 0 || (n > 0 && (!queries || !out))) return PBR_E_INVALID;
     return probe_round_trip(ctx, n, queries, (size_t)n * 36, out, (size_t)n * 20,

@@ -1532,6 +1532,29 @@ __device__ __forceinline__ bool make_bsdf(const DeviceScene& S, const MatTemplat
     return true;
 }
 
+// One mirror step of the followed feature pass (pbr_hip_render_aov_mirrors): what
+// Whitted's SpecularReflect does at a Mirror hit whose clamped, texture-evaluated Kr is kr.  The frame
+// is make_bsdf's, the lobe lobe_sample's L_SPEC_R with the no-op Fresnel (f = Kr / |cos|, pdf = 1), the
+// refusals k_wf_shade's: wo in the shading tangent plane (Sample_f returns before a pdf is set), a black
+// f, a wi perpendicular to ns.  No sampler value is read.  True: *next = spawn_ray(it, wi).
+PBR_HD bool mirror_step(const Isect& it, rgb kr, Ray* next) {
+    BSDF b;
+    b.mt = nullptr;
+    b.ns = it.sn;
+    b.ng = it.n;
+    b.ss = normalize(it.dpdu);
+    b.ts = cross(b.ns, b.ss);
+    const f3 wo = b.to_local(it.wo);
+    if (wo.z == 0) return false;
+    const f3 wl = mk(-wo.x, -wo.y, wo.z);
+    const rgb f = kr / fabsf(wl.z);
+    if (black(f)) return false;
+    const f3 wi = b.to_world(wl);
+    if (absdot(wi, it.sn) == 0.f) return false;
+    *next = spawn_ray(it, wi);
+    return true;
+}
+
 // ---------------------------------------------------------------- lights (Light/*.cpp)
 PBR_HD rgb area_L(const DLight& l, f3 n, f3 w) { return (l.twoSided || dot(n, w) > 0) ? ld3(l.L) : sp(0.f); }
 PBR_HD void sphere_uv(f3 p, float* u, float* v) {   // SkyBoxLight.cpp:12-17

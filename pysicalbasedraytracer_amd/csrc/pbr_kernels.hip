@@ -2849,7 +2849,14 @@ int pbr_hip_plan_aov(int64_t n_pixels, int samples, int max_launches, int64_t* f
 }
 
 int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sample, int samples, float* accum, float* aov_out) {
+    return pbr_hip_render_aov_mirrors(ctx, d, 0, first_sample, samples, accum, aov_out);
+}
+
+// max_bounces > 0: the FOLLOW instantiations (pbr_aov.h), under profile families of their own; 0: the plain call's launches
+int pbr_hip_render_aov_mirrors(pbr_hip_ctx* ctx, const pbr_render_desc* d, int max_bounces, int first_sample, int samples,
+                               float* accum, float* aov_out) {
     if (!ctx) return PBR_E_INVALID;
+    if (max_bounces < 0 || max_bounces > kAovMaxBounces) return set_err(ctx, PBR_E_INVALID, "render_aov: max_bounces must be in 0..16");
     long long budget = 0;
     if (int rc = check_pass(ctx, kAov, d, first_sample, samples, 1, accum, &budget)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -2878,18 +2885,25 @@ int pbr_hip_render_aov(pbr_hip_ctx* ctx, const pbr_render_desc* d, int first_sam
     A.accum = accum;
     A.out = aov_out;
     A.albedo = (const float4*)ctx->dAlbedo.p;
+    A.maxBounces = max_bounces;
     const bool tex = !ctx->host.texMats.empty(), binary = P.S.binaryWalk != 0;
     const bool nrm = !ctx->host.triN.empty();   // (NRM: pbr_device.h triangle_normals_frame)
-    const int kind = tex ? KP_AOV_TEX : KP_AOV;
+    const bool follow = max_bounces > 0;
+    const int kind = follow ? (tex ? KP_AOV_FOLLOW_TEX : KP_AOV_FOLLOW) : (tex ? KP_AOV_TEX : KP_AOV);
     ctx->batchFrames = 0;   // (set when the pass is queued)
     begin_lanes(ctx, s);
     for (const AovLaunch& l : aov_launches(npx, samples)) {
         A.pix0 = l.pix0;
         A.pixEnd = l.pix0 + l.nPix;
         const dim3 grid((unsigned)((l.nPix + P.ppb - 1) / P.ppb)), blk(kAovBlock);
-        PROF_LAUNCH(kind, s,
-            if (tex) { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (true, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (true, false), grid, blk, 0, s, A); }
-            else { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (false, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (false, false), grid, blk, 0, s, A); });
+        if (follow)
+            PROF_LAUNCH(kind, s,
+                if (tex) { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (true, true, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (true, false, true), grid, blk, 0, s, A); }
+                else { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (false, true, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (false, false, true), grid, blk, 0, s, A); });
+        else
+            PROF_LAUNCH(kind, s,
+                if (tex) { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (true, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (true, false), grid, blk, 0, s, A); }
+                else { if (binary) PBR_LAUNCH_NRM(nrm, k_aov, (false, true), grid, blk, 0, s, A); else PBR_LAUNCH_NRM(nrm, k_aov, (false, false), grid, blk, 0, s, A); });
     }
     HIP_TRY(hipGetLastError());
     prof_host(ctx, kind, 0, (unsigned long long)npx * (unsigned long long)samples);
@@ -3139,7 +3153,8 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         "k_wfp_camera_extend", "k_wfp_shade", "k_wfp_shadow", "k_wfp_probe", "k_wfp_resolve", "k_wfp_finish",
         "k_wfv_shade", "k_wfv_tr", "k_wfv_resolve", "k_render", "k_wf_shade_l0", "k_aov", "k_aov_tex",
         "k_dn_prepare", "k_dn_atrous_l0", "k_dn_atrous_l1", "k_dn_atrous_l2", "k_dn_atrous_l3", "k_dn_atrous_l4",
-        "k_dn_atrous_l5", "k_dn_atrous_l6", "k_dn_atrous_l7", "k_dn_finish", "k_tp_accumulate", "k_dn_spatial"};
+        "k_dn_atrous_l5", "k_dn_atrous_l6", "k_dn_atrous_l7", "k_dn_finish", "k_tp_accumulate", "k_dn_spatial",
+        "k_aov_follow", "k_aov_follow_tex"};
     unsigned long long c[KP_COUNT][kProfFields];
     std::memset(c, 0, sizeof(c));
     if (ctx->profOn) HIP_TRY(hipMemcpy(c, ctx->dProf.p, sizeof(c), hipMemcpyDeviceToHost));
@@ -3182,7 +3197,7 @@ int pbr_hip_get_profile(pbr_hip_ctx* ctx, pbr_kernel_profile* out, int max, int*
         case KP_WFV_TR: return 100 * f[0];
         case KP_WFV_RESOLVE: return 140 * f[0];
         // f[1] pixels: the sums written; f[2] of them continue (the sums read); f[3] write the image
-        case KP_AOV: case KP_AOV_TEX: return 32 * (f[1] + f[2] + f[3]);
+        case KP_AOV: case KP_AOV_TEX: case KP_AOV_FOLLOW: case KP_AOV_FOLLOW_TEX: return 32 * (f[1] + f[2] + f[3]);
         // the denoiser, f[0] pixels.  prepare: sums 24 + features 32 (+ 4 per count, f[1]) read, three
         // planes written; a level: colour and guides read, colour written; finish: colour and divisor
         // read, f[1] rgb, f[2] rgba and f[3] variance pixels written

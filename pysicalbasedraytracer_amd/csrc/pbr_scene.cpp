@@ -610,7 +610,7 @@ void build_host_scene(const pbr_scene_desc* d, HostScene* S, const BvhBuildFn* b
     }
     S->albedo.assign((size_t)4 * d->n_materials, 0.f);
     for (int m = 0; m < d->n_materials; ++m)
-        S->albedo[4 * m + 3] = material_albedo(mat_params(d->materials[m]), &S->albedo[4 * m]) ? 1.f : 0.f;
+        S->albedo[4 * m + 3] = material_albedo(mat_params(d->materials[m]), &S->albedo[4 * m]) ? (float)d->materials[m].type : 0.f;
     // 4b. image textures (ImageTexture, Texture/ImageTexture.cpp) and the materials that read them:
     //     those get their lobes per hit (pbr_device.h textured_template)
     if (d->n_textures < 0 || (d->n_textures > 0 && !d->textures)) fail("bad textures");

@@ -65,7 +65,7 @@ struct HostScene {
     std::vector<TexDev> textures;           // ImageTextures (level 0 + mapping)
     std::vector<float> texTexels;           // their texels, 4 floats each
     std::vector<TexMat> texMats;            // per material, only when some material is textured
-    std::vector<float> albedo;              // 4 floats per material: material_albedo of its constants, 1 if it has a BSDF
+    std::vector<float> albedo;              // 4 floats per material: material_albedo of its constants, its pbr_material_type (0: no BSDF)
 };
 
 // InfiniteAreaLight tables (Light/InfiniteAreaLight.cpp:7-61): the level-0 MIPMap image (resampled

@@ -46,6 +46,7 @@ enum ProfKind {
     KP_DN_PREPARE, KP_DN_LEVEL0, KP_DN_FINISH = KP_DN_LEVEL0 + 8,
     KP_TP_ACCUMULATE,   // the temporal merge (pbr_temporal.h)
     KP_DN_SPATIAL,      // the denoiser's spatial variance estimate (pbr_denoise.h), appended: the kinds above keep their indices
+    KP_AOV_FOLLOW, KP_AOV_FOLLOW_TEX,   // feature passes that follow mirror bounces (pbr_aov.h FOLLOW), appended likewise
     KP_COUNT
 };
 constexpr int kProfFields = 8;

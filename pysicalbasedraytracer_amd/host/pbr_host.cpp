@@ -1616,9 +1616,10 @@ std::vector<int> SamplerIntegrator::RenderAdaptive(const Scene& scene, int minSa
     return RenderPass(scene, "RenderAdaptive", 0, 0, &a);
 }
 
-void SamplerIntegrator::RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out) {
+void SamplerIntegrator::RenderFeatures(const Scene& scene, int firstSample, int nSamples, FeatureBuffers* out, int mirrorBounces) {
     const std::string who("RenderFeatures");
     if (firstSample < 0 || nSamples < 1) throw std::invalid_argument(who + ": firstSample >= 0 and nSamples >= 1");
+    if (mirrorBounces < 0 || mirrorBounces > 16) throw std::invalid_argument(who + ": mirrorBounces must be 0..16");
     if (!out) throw std::invalid_argument(who + ": out == nullptr");
     if (!devices.empty()) throw std::invalid_argument(who + ": one device (SetDevice), not SetDevices");
     FrameRequest q(*this, scene, who);   // (its integrator, depth and light strategy are not read by a feature pass)
@@ -1626,7 +1627,7 @@ void SamplerIntegrator::RenderFeatures(const Scene& scene, int firstSample, int 
     const size_t px = PBR_AOV_CHANNELS * sizeof(float);
     PassBuffers::continue_at(feat, *this, scene, who, firstSample, featuresDone, q.npx, {px, px});
     float *accum = (float*)feat->p[0], *image = (float*)feat->p[1];
-    check(ctx, pbr_hip_render_aov(ctx, &q.rd, firstSample, nSamples, accum, image), "pbr_hip_render_aov");
+    check(ctx, pbr_hip_render_aov_mirrors(ctx, &q.rd, mirrorBounces, firstSample, nSamples, accum, image), "pbr_hip_render_aov_mirrors");
     check(ctx, pbr_hip_sync(ctx), "pbr_hip_sync");
     featuresDone = firstSample + nSamples;
     const int W = q.W, H = q.H;
